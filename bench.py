@@ -23,7 +23,13 @@ its own done flags, its frame into the ring and its masks into its own buffer;
 one stream, every foreign call bound before the region (ObsLoop).  The other
 modes ('serial', 'pipe': dt_step + dt_copy_pose + dt_render of the snapshot
 on a second stream, the form an actor-in-the-loop consumer uses; 'many2')
-compute the same outputs.  After it, outside the timed region:
+compute the same outputs.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up,
+times the K decisions and prints the line: value, ms_per_step (the wall time
+of one timed decision), the counts.  --dump-outputs DIR writes what the last
+timed decision returned (dump_outputs) before the line.  Everything below is
+behind --full, after the timed region and outside it:
   * parity: the C oracle (oracle/dtsim_oracle.c, test infrastructure) re-runs
     every env of this rank from the saved start state through the same actions;
     reward/reward_mod/obs/done of every decision and the end pose/counters are
@@ -37,11 +43,17 @@ compute the same outputs.  After it, outside the timed region:
     ring refill of respawned envs) / its mean duration from HIP events on the
     render stream;
   * config2: BASELINE configs[1] (lane-pose obs only, dt_step_many launches) as
-    a sub-record with its own parity and roofline.
+    a sub-record with its own parity and roofline;
+  * config4 / config5 (float32 and fp16 acting) as sub-records, and the CPU
+    baselines of each record.
+A timed region longer than --parity-steps (100) decisions is not re-run by the
+oracle (each decision's kept masks are 314 MB); parity then checks a pass of
+--parity-steps further decisions of the same launch form.
 
 Other configs: --config lane (configs[1] as the headline), actor = configs[3]
 (actor in the loop), train = configs[4] (full DDPG: rollout + GPU prioritized
-replay + update + RCCL gradient all-reduce).
+replay + update + RCCL gradient all-reduce); their parity and CPU baselines
+are behind --full too.
 
 N > 1: `python bench.py --gpus N` starts torch.distributed.run with N ranks as
 a child process BEFORE anything touches the GPU (the driver may also launch
@@ -161,7 +173,25 @@ def parse(argv=None):
                    help='CPU baseline processes (0 = the box CPU share: min(16, affinity))')
     p.add_argument('--dry-run', action='store_true',
                    help='launcher/reduction check on CPU over gloo, no kernels')
-    return p.parse_args(argv)
+    p.add_argument('--full', action='store_true',
+                   help='beside the headline figure: the oracle parity pass, the roofline '
+                        'pass, the sub-records (configs 2, 4, 5) and the CPU baselines; a '
+                        'plain run sets up, warms up, times --steps decisions and prints the '
+                        'line')
+    p.add_argument('--parity-steps', type=int, default=100,
+                   help='--full, render: most timed decisions the oracle re-runs; after a '
+                        'longer timed region the parity pass checks this many further '
+                        'decisions of the same launch form instead')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='render / lane: after the timed decisions write what the last one '
+                        'returned to its caller as DIR/<name>.npy (float32 / float64; the '
+                        'frames and masks of a fixed seeded sample of --dump-envs envs)')
+    p.add_argument('--dump-envs', type=int, default=64,
+                   help='--dump-outputs: envs whose frame stack and masks are written')
+    args = p.parse_args(argv)
+    if args.dump_outputs and args.config in ('actor', 'train'):
+        p.error('--dump-outputs covers --config render and lane')
+    return args
 
 
 # ---- N-rank launcher ---------------------------------------------------------------
@@ -543,7 +573,8 @@ def main(argv=None):
     if args.config == 'train':
         return bench_train(args, ctx)
     if args.config == 'lane':
-        line = lane_record(args, ctx, args.steps, args.warmup, cpu=True)
+        line = lane_record(args, ctx, args.steps, args.warmup, cpu=args.full,
+                           headline=True)
         if ctx.rank == 0:
             print(json.dumps(line), flush=True)
         ctx.close()
@@ -735,6 +766,36 @@ class ObsLoop:
         return rcs
 
 
+def dump_outputs(args, ctx, env, out, ro=None, masks=None):
+    """--dump-outputs: what the last timed decision handed its caller, one
+    DIR/<name>.npy each (rank r > 0: <name>_rank<r>.npy): the step outputs and
+    the end state of every env in float64 (done as float32), and of a fixed
+    seeded sample of --dump-envs envs the frame stack (oldest first) and the
+    four line masks in float32 (64 envs: 35 MB).  Same arguments, same arrays."""
+    torch = ctx.torch
+    n = env.n
+    ctx.sync()
+    last = _Slice(out, out.reward.numel() // n - 1, out.reward.numel() // n, n)
+    arrs = {'reward': last.reward.double(), 'reward_mod': last.reward_mod.double(),
+            'done': last.done.float(), 'obs': last.obs.view(n, 2).double()}
+    arrs = {k: v.cpu().numpy() for k, v in arrs.items()}
+    st = env.get_state()
+    for k in ('x', 'z', 'angle', 'step_count', 'env_step', 'episode'):
+        arrs['state_' + k] = np.asarray(st[k], dtype=np.float64)
+    if ro is not None:
+        m = max(1, min(n, args.dump_envs))
+        idx = np.sort(np.random.default_rng(args.seed).choice(n, m, replace=False))
+        sel = torch.as_tensor(idx, device=env.device)
+        from aido1_amd.render import as_gray
+        arrs['sample_envs'] = idx.astype(np.float64)
+        arrs['frames'] = as_gray(ro.ring.index_select(0, sel)[:, ro.order()]).float().cpu().numpy()
+        arrs['masks'] = masks.index_select(0, sel).float().cpu().numpy()
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    tag = '_rank%d' % ctx.rank if ctx.rank else ''
+    for k, v in arrs.items():
+        np.save(os.path.join(args.dump_outputs, k + tag + '.npy'), v)
+
+
 def bench_obs(args, ctx):
     torch = ctx.torch
     from aido1_amd.config import EnvConfig
@@ -748,9 +809,14 @@ def bench_obs(args, ctx):
     g.manual_seed(args.seed + 7919 * rank)
     actions = torch.rand(W + K, n, 2, generator=g, device=dev, dtype=torch.float32)
     ro = RenderOutput(n, dev)          # 3-slot grey ring (Transformer stack) + 4 masks
+    # --full: parity re-runs the timed decisions, each one's masks kept (314 MB a
+    # decision at 4096 envs), up to --parity-steps of them; a longer timed
+    # region keeps none and is followed by a parity pass of its own
+    check = args.full and not args.no_parity
+    timed_check = check and K <= args.parity_steps
     loop = ObsLoop(env, ro, torch, args.obs_mode, args.many, args.event_stride,
                    group=1 if args.no_pair else args.render_group,
-                   keep_masks=0 if args.no_parity else K)
+                   keep_masks=K if timed_check else 0)
     env.reset()
     wout = StepOutput(max(W, 1) * n, dev, lanepos=False, tile=False)
     if W and loop.run(loop.bind(actions[:W], wout), loop.events(W)):
@@ -778,15 +844,80 @@ def bench_obs(args, ctx):
                if li % loop.event_stride == 0]
     starts = [g[0] for g in calls]
     step_ms = [ev[2][d][0].elapsed_time(ev[2][d][1]) for d in starts]
+    if args.dump_outputs:
+        dump_outputs(args, ctx, env, out, ro, loop.last_masks)
+    line = {
+        'metric': METRIC, 'value': tot[0] / tmax, 'unit': 'env-steps/s',
+        'n_gpus': ctx.world, 'steps': K, 'warmup': W,
+        'ms_per_step': tmax / K * 1e3, 'higher_is_better': True,
+        'scaling': 'weak', 'vs_baseline': None,
+        'dtype': 'f64 step / f32 raster + grey / u8 masks',
+        'data': 'synthetic', 'full': bool(args.full),
+        'config': {'workload': 'config3: %d envs/GPU, lane pose + 120x160 top-down render + '
+                               'grey frame ring + line_detector1 HSV/edge masks' % n,
+                   'map': args.map, 'envs_per_gpu': n, 'global_envs': n * ctx.world,
+                   'repeat_actions': 3, 'auto_reset': True,
+                   'actions': 'U[0,1)^2 wheel velocities, resident in HBM',
+                   'launch': {
+                       'many': 'dt_step_many over chunks of <= %d decisions (each '
+                               'decision\'s end pose written), then the chunk\'s renders, '
+                               'each of its decision\'s pose with its done flags as fresh, '
+                               '%s; one stream, prebound calls'
+                               % (args.many, '%d consecutive decisions a launch '
+                                  '(dt_render%d, each decision its own masks buffer)'
+                                  % (loop.group, loop.group) if loop.group > 1
+                                  else 'one decision a launch (dt_render)'),
+                       'many2': 'dt_step_many over chunks of <= %d decisions on a step '
+                                'stream (each decision\'s end pose written, two pose '
+                                'buffers), each decision\'s dt_render of that pose on a '
+                                'render stream: chunk c + 1\'s steps beside chunk c\'s '
+                                'renders; prebound calls' % args.many,
+                       'serial': 'per decision: dt_step then dt_render, one stream, prebound',
+                       'pipe': 'per decision: dt_step + dt_copy_pose (high-priority stream), '
+                               'dt_render of the snapshot (render stream), prebound'
+                   }[args.obs_mode],
+                   'parallelism': 'env shards (%d x %d), no collective' % (ctx.world, n)},
+        'counts': {'env_steps': tot[0], 'decisions': tot[1], 'resets': tot[2],
+                   'elapsed_s': tmax},
+        'per_rank': per,
+        'process_group': {'backend': 'nccl (RCCL)' if ctx.pg else None,
+                          'world': ctx.dist.get_world_size() if ctx.pg else 1},
+        'step_launch_ms': float(np.mean(step_ms)),
+        'step_launches': len(starts),
+        'host_enqueue_ms_per_step': t_host / K * 1e3,
+    }
+    if not args.full:
+        # the plain run ends here: the headline figure alone
+        env.close()
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        ctx.close()
+        return
 
     parity = None
-    if not args.no_parity:
-        # every timed decision's masks (each its own buffer), or the last one's
+    if check:
         import types
+        p_start, p_act, p_out, p_loop = start, actions[W:], out, loop
+        if not timed_check:
+            # a parity pass of its own: --parity-steps further decisions in the
+            # timed region's launch form, every decision's masks kept
+            P = max(ro.slots, args.parity_steps)
+            p_loop = ObsLoop(env, ro, torch, args.obs_mode, args.many, args.event_stride,
+                             group=1 if args.no_pair else args.render_group, keep_masks=P)
+            p_act = torch.rand(P, n, 2, generator=g, device=dev, dtype=torch.float32)
+            p_out = StepOutput(P * n, dev, lanepos=False, tile=False)
+            p_start = env.get_state()
+            if p_loop.run(p_loop.bind(p_act, p_out), p_loop.events(P)):
+                raise RuntimeError('a call of the parity pass failed')
+            ctx.sync()
+        # every checked decision's masks (each its own buffer), or the last one's
         frames = types.SimpleNamespace(slots=ro.slots, stack_view=ro.stack_view,
-                                       masks=loop.last_masks,
-                                       dmasks=loop.dmasks if loop.kept else None)
-        parity = step_parity(env, start, actions[W:], out, rank, args, frames=frames)
+                                       masks=p_loop.last_masks,
+                                       dmasks=p_loop.dmasks if p_loop.kept else None)
+        parity = step_parity(env, p_start, p_act, p_out, rank, args, frames=frames)
+        parity['of'] = 'the timed decisions' if timed_check else \
+            'a pass of %d decisions after the timed region' % P
+        del p_loop, p_out, frames
     parity = worst_over_ranks(ctx, parity, STEP_PARITY_KEYS + ['gray_mismatches',
                                                                'mask_mismatches'])
     # the roofline's kernel time: an event-only pass after the timed region
@@ -846,42 +977,7 @@ def bench_obs(args, ctx):
         per_launch_dec = KE / nl
         achieved = bpl / (kms * 1e-3) / 1e9
         pmc = load_pmc('render_kernel') or {}
-        line = {
-            'metric': METRIC, 'value': tot[0] / tmax, 'unit': 'env-steps/s',
-            'n_gpus': ctx.world, 'steps': K, 'warmup': W,
-            'ms_per_step': tmax / K * 1e3, 'higher_is_better': True,
-            'scaling': 'weak', 'vs_baseline': None,
-            'dtype': 'f64 step / f32 raster + grey / u8 masks',
-            'data': 'synthetic',
-            'config': {'workload': 'config3: %d envs/GPU, lane pose + 120x160 top-down render + '
-                                   'grey frame ring + line_detector1 HSV/edge masks' % n,
-                       'map': args.map, 'envs_per_gpu': n, 'global_envs': n * ctx.world,
-                       'repeat_actions': 3, 'auto_reset': True,
-                       'actions': 'U[0,1)^2 wheel velocities, resident in HBM',
-                       'launch': {
-                           'many': 'dt_step_many over chunks of <= %d decisions (each '
-                                   'decision\'s end pose written), then the chunk\'s renders, '
-                                   'each of its decision\'s pose with its done flags as fresh, '
-                                   '%s; one stream, prebound calls'
-                                   % (args.many, '%d consecutive decisions a launch '
-                                      '(dt_render%d, each decision its own masks buffer)'
-                                      % (loop.group, loop.group) if loop.group > 1
-                                      else 'one decision a launch (dt_render)'),
-                           'many2': 'dt_step_many over chunks of <= %d decisions on a step '
-                                    'stream (each decision\'s end pose written, two pose '
-                                    'buffers), each decision\'s dt_render of that pose on a '
-                                    'render stream: chunk c + 1\'s steps beside chunk c\'s '
-                                    'renders; prebound calls' % args.many,
-                           'serial': 'per decision: dt_step then dt_render, one stream, prebound',
-                           'pipe': 'per decision: dt_step + dt_copy_pose (high-priority stream), '
-                                   'dt_render of the snapshot (render stream), prebound'
-                       }[args.obs_mode],
-                       'parallelism': 'env shards (%d x %d), no collective' % (ctx.world, n)},
-            'counts': {'env_steps': tot[0], 'decisions': tot[1], 'resets': tot[2],
-                       'elapsed_s': tmax},
-            'per_rank': per,
-            'process_group': {'backend': 'nccl (RCCL)' if ctx.pg else None,
-                              'world': ctx.dist.get_world_size() if ctx.pg else 1},
+        line.update({
             'parity': parity,
             'roofline': {'bound': 'hbm', 'kernel': 'render_kernel', 'achieved': achieved,
                          'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS,
@@ -907,15 +1003,12 @@ def bench_obs(args, ctx):
                                    'timed_region_sampled_ms: events around every %d-th '
                                    'dt_render inside the timed region (%d launches)'
                                    % (KE, len(rend_all), loop.event_stride, len(rend_ms))},
-            'step_launch_ms': float(np.mean(step_ms)),
-            'step_launches': len(starts),
-            'host_enqueue_ms_per_step': t_host / K * 1e3,
             'config2': lane,
             'config4': c4,
             'config4_fp16': c4h,
             'config5': c5,
             'config5_fp16': c5h,
-        }
+        })
         line['cpu_baseline'] = (cpu_obs_baseline(args.cpu_decisions, args.cpu_procs, args.map)
                                 if ctx.world == 1 and args.cpu_steps > 0 else None)
         print(json.dumps(line), flush=True)
@@ -923,10 +1016,11 @@ def bench_obs(args, ctx):
 
 
 # ---- config 2 ------------------------------------------------------------------------------
-def lane_record(args, ctx, K, W, cpu):
+def lane_record(args, ctx, K, W, cpu, headline=False):
     """BASELINE configs[1]: lane-pose obs only; the K timed decisions split into
     equal dt_step_many launches of at most --many decisions, each one prebound
-    foreign call (--graph: one captured HIP graph)."""
+    foreign call (--graph: one captured HIP graph).  headline: the line itself
+    (--config lane), not the render line's sub-record."""
     torch = ctx.torch
     from aido1_amd.config import EnvConfig
     from aido1_amd.vec_env import StepOutput, VecEnv
@@ -981,7 +1075,10 @@ def lane_record(args, ctx, K, W, cpu):
     launches_ms = e0.elapsed_time(e1)
     tot, tmax, per = rank_report(ctx, [st['sim_steps'], st['decisions'], st['resets']], elapsed)
     sim_steps, decisions, resets = tot
-    parity = None if args.no_parity else step_parity(env, start, actions[W:], out, rank, args)
+    if args.dump_outputs and headline:
+        dump_outputs(args, ctx, env, out)
+    parity = None if args.no_parity or not args.full else \
+        step_parity(env, start, actions[W:], out, rank, args)
     parity = worst_over_ranks(ctx, parity, STEP_PARITY_KEYS)
     env.close()
     if rank != 0:
@@ -1363,9 +1460,10 @@ def actor_roofline(torch, dtype, n, actor_ms, frame_b):
 
 def bench_actor(args, ctx):
     torch = ctx.torch
-    line = actor_record(args, ctx, args.steps, args.warmup, parity=not args.no_parity,
+    line = actor_record(args, ctx, args.steps, args.warmup,
+                        parity=args.full and not args.no_parity,
                         dtype=torch.float32 if args.actor_dtype == 'float32' else torch.float16,
-                        cpu=True)
+                        cpu=args.full)
     if line is not None:
         print(json.dumps(line), flush=True)
     ctx.close()
@@ -1496,7 +1594,8 @@ def train_record(args, ctx, K, W, parity=True, cpu=False, dtype=None):
 
 
 def bench_train(args, ctx):
-    line = train_record(args, ctx, args.steps, args.warmup, parity=not args.no_parity)
+    line = train_record(args, ctx, args.steps, args.warmup,
+                        parity=args.full and not args.no_parity)
     if line is not None:
         print(json.dumps(line), flush=True)
     ctx.close()

@@ -54,6 +54,17 @@ def test_world_size_must_match_gpus():
     assert 'WORLD_SIZE=1 but --gpus 2' in r.stderr
 
 
+def test_full_and_dump_options():
+    sys.path.insert(0, REPO)
+    import bench
+    a = bench.parse(['--gpus', '1', '--steps', '7', '--warmup', '2'])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7
+    a = bench.parse(['--full', '--dump-outputs', 'out'])
+    assert a.full is True and a.dump_outputs == 'out'
+    with pytest.raises(SystemExit):     # the actor / train configs have no dump
+        bench.parse(['--config', 'train', '--dump-outputs', 'out'])
+
+
 def test_split_even():
     sys.path.insert(0, REPO)
     import bench

@@ -1,12 +1,13 @@
 #!/bin/bash
 # A/B of a build switch: bench.py with the product library and a diagnostic
 # build (DTSIM_DIAG_LIB=<lib>), alternated R times; one summary line a run.
-# usage: tools/ab.sh <diag .so> <R> [bench args...]  (default: the render bench)
+# usage: tools/ab.sh <diag .so> <R> [bench args...]  (default: the render bench; the
+# summary reads the roofline record, so bench args of your own include --full)
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 lib=$1; R=${2:-3}; shift 2
 args=("$@")
-[ ${#args[@]} -eq 0 ] && args=(--steps 100 --warmup 20 --cpu-steps 0 --no-lane --no-sub --no-parity \
+[ ${#args[@]} -eq 0 ] && args=(--full --steps 100 --warmup 20 --cpu-steps 0 --no-lane --no-sub --no-parity \
                                --event-stride 1)
 for i in $(seq 1 "$R"); do
   for v in product diag; do

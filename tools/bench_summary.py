@@ -1,4 +1,4 @@
-"""Print the headline and sub-record figures of a bench.py JSON line."""
+"""Print the headline and sub-record figures of a `bench.py --full` JSON line."""
 import json
 import sys
 

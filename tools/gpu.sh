@@ -3,7 +3,7 @@
 # usage: tools/gpu.sh TAG STEP [STEP ...]
 #   suite [pytest args]   the whole GPU suite, one process (TESTS=... narrows it)
 #   smoke                 __graft_entry__.smoke()
-#   driver                bench.py exactly as the driver runs it (--gpus 1 --steps 20 --warmup 5)
+#   driver                bench.py --gpus 1 --steps 20 --warmup 5 --full (parity, roofline, sub-records)
 #   bench:<args>          bench.py with <args> (commas become spaces)
 #   prof:<config>         rocprofv3 --kernel-trace --stats of bench.py --config <config>
 #   py:<script>[,args]    a tools/ python script
@@ -48,13 +48,13 @@ for st in "$@"; do
     suite) run suite 900 python -u -m pytest ${TESTS:-tests} -m gpu -v -x --timeout 200 \
              --timeout-method thread $args ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    driver) run driver 600 python bench.py --gpus 1 --steps 20 --warmup 5
+    driver) run driver 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full
             summ "gpurun_out/${TAG}_${i}_driver.log" ;;
     bench) run bench 600 python bench.py $args; summ "gpurun_out/${TAG}_${i}_bench.log" ;;
     prof) rm -rf "/tmp/prof_$arg"
           run "prof_$arg" 600 rocprofv3 --kernel-trace --stats --output-format csv \
             -d "/tmp/prof_$arg" -o run -- python3 "$ROOT/bench.py" --config "$arg" \
-            --steps 20 --warmup 5 --cpu-steps 0 --no-parity
+            --full --steps 20 --warmup 5 --cpu-steps 0 --no-parity
           f=$(find "/tmp/prof_$arg" -name '*kernel_stats.csv' | head -1)
           cp "$f" "gpurun_out/${TAG}_${arg}_kernel_stats.csv"
           cp "${f%_kernel_stats.csv}_kernel_trace.csv" "gpurun_out/${TAG}_${arg}_kernel_trace.csv"

@@ -13,7 +13,7 @@ for ctr in $SETS; do
   i=$((i+1))
   rm -rf "/tmp/kpmc_$i"
   timeout -k 10 -s KILL 180 rocprofv3 --pmc ${ctr//,/ } --output-format csv -d "/tmp/kpmc_$i" -o run -- \
-    python3 "$ROOT/bench.py" --config "$CFG" --steps 5 --warmup 3 --cpu-steps 0 --no-parity \
+    python3 "$ROOT/bench.py" --full --config "$CFG" --steps 5 --warmup 3 --cpu-steps 0 --no-parity \
     > "gpurun_out/kpmc_$i.log" 2>&1 || { echo "fail $i"; tail -5 "gpurun_out/kpmc_$i.log"; exit 1; }
   f=$(find "/tmp/kpmc_$i" -name '*counter_collection.csv' | head -1)
   python3 - "$f" $NEEDLES <<'PY'

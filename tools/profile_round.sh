@@ -17,14 +17,14 @@ step() {  # step <name> <timeout> cmd...
   [ $rc -eq 0 ] || { echo "stopping"; exit $rc; }
 }
 declare -A ARGS=(
-  [lane]="--config lane --steps $STEPS --warmup 20 --cpu-steps 0 --no-sub"
-  [render]="--config render --steps 100 --warmup 20 --cpu-steps 0 --no-lane --no-sub"
-  [actor]="--config actor --steps 30 --warmup 5 --cpu-steps 0"
-  [train]="--config train --steps 30 --warmup 10 --cpu-steps 0")
+  [lane]="--full --config lane --steps $STEPS --warmup 20 --cpu-steps 0 --no-sub"
+  [render]="--full --config render --steps 100 --warmup 20 --cpu-steps 0 --no-lane --no-sub"
+  [actor]="--full --config actor --steps 30 --warmup 5 --cpu-steps 0"
+  [train]="--full --config train --steps 30 --warmup 10 --cpu-steps 0")
 # plain runs first (no profiler): the bench lines DESIGN quotes
 if [ -z "$NO_PLAIN" ]; then
-  step bench_driver 400 python3 "$ROOT/bench.py"
-  step bench_lane_320 300 python3 "$ROOT/bench.py" --config lane --steps 320 --warmup 20 --cpu-steps 0
+  step bench_driver 400 python3 "$ROOT/bench.py" --full
+  step bench_lane_320 300 python3 "$ROOT/bench.py" --full --config lane --steps 320 --warmup 20 --cpu-steps 0
   for cfg in render actor train; do step "bench_$cfg" 600 python3 "$ROOT/bench.py" ${ARGS[$cfg]}; done
   step bench_actor_eval 600 python3 "$ROOT/bench.py" ${ARGS[actor]} --actor-mode eval
 fi

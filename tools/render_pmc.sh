@@ -10,7 +10,7 @@ for ctr in $SETS; do
   i=$((i+1))
   if [ -n "$GROUP" ]; then   # the bench's grouped launches (dt_step_many + dt_render3)
     timeout -k 10 -s KILL 180 rocprofv3 --pmc ${ctr//,/ } --output-format csv -d "$ROOT/gpurun_out/rpmc_$i" -o run -- \
-      python3 "$ROOT/bench.py" --config render --steps 40 --warmup 10 --cpu-steps 0 --no-lane --no-sub \
+      python3 "$ROOT/bench.py" --full --config render --steps 40 --warmup 10 --cpu-steps 0 --no-lane --no-sub \
       --no-parity > "gpurun_out/rpmc_$i.log" 2>&1 || { echo "fail $i"; tail -5 gpurun_out/rpmc_$i.log; exit 1; }
   else
     TIME_ONLY=1 timeout -k 10 -s KILL 120 rocprofv3 --pmc ${ctr//,/ } --output-format csv -d "$ROOT/gpurun_out/rpmc_$i" -o run -- \
