@@ -1,8 +1,10 @@
 // The DDPG update's convolutions (include/dtupd.h): config.json's conv_2d
-// layers of the actor and critic in f32, forward (x3: f32 operands as fp16
-// hi / lo pairs on v_mfma_f32_32x32x16_f16, DTUPD_X3 below), weight gradient
-// and input gradient (v_mfma_f32_32x32x2_f32), replacing MIOpen in the
-// train-mode networks of training/trainers.py:143-237.
+// layers of the actor and critic at f32 accuracy, replacing MIOpen in the
+// train-mode networks of training/trainers.py:143-237.  The forward, the
+// input gradient and the weight gradient of conv1, conv2 and conv4 run x3
+// (f32 operands as fp16 hi / lo pairs on v_mfma_f32_32x32x16_f16, DTUPD_X3
+// below; the gradients' dZ scaled by a power of two first, DTUPD_DZ_SCALE);
+// conv3's weight gradient and the linears run v_mfma_f32_32x32x2_f32.
 //
 // Every layer is C_out = 32 and NHWC, so each pass is a GEMM whose N or M is
 // the 32 channels:
@@ -66,6 +68,10 @@
 #ifndef DTUPD_DG4_NW
 #define DTUPD_DG4_NW 4
 #endif
+// weight gradient: dZ rows of the max |dZ| pass in flight at once
+#ifndef DTUPD_WG_PRE_UNROLL
+#define DTUPD_WG_PRE_UNROLL 4
+#endif
 
 namespace {
 
@@ -108,14 +114,21 @@ __device__ __forceinline__ float4 ld4(const float* p) {
   }
 }
 
-// The forward's x3 form (DTUPD_X3, the library default): each f32 operand
-// as an fp16 pair hi = fp16(v), lo = fp16((v - hi) * 2^11), and a 16-k unit
-// as three v_mfma_f32_32x32x16_f16 into two f32 accumulators,
+// The x3 form of the forward and of both gradients (DTUPD_X3, the library
+// default): each f32 operand as an fp16 pair hi = fp16(v), lo = fp16((v - hi)
+// * 2^11), and a 16-k unit as three v_mfma_f32_32x32x16_f16 into two f32
+// accumulators,
 //   acc0 += Xh Wh,   acc1 += Xh Wl + Xl Wh,   z = acc0 + acc1 / 2^11
 // (the dropped Xl Wl and the split's rounding: ~2^-21 of each product, the
 // actor's conv chain, csrc/dtconvx.hip), 3/16 of the f32 MFMA cycles.
-// Operands past fp16's range (|v| >= 65520) become inf: the guard reports
-// them.  0 keeps the f32 MFMA chain (tools/upd_micro.py variants).
+// The pair carries v to max(2^-23 |v|, 2^-36): f32 accuracy for operands of
+// order 1 (frames, BatchNorm outputs, weights), fewer bits the further v
+// lies below 2^-14, where hi is an fp16 subnormal (gfx950 keeps those, it
+// does not flush them): 2^-6 relative at 2^-30, nothing at 2^-37.  The
+// gradients' dZ, which lives down there, is scaled into range first
+// (DTUPD_DZ_SCALE below).  Unscaled operands past fp16's range (|v| >=
+// 65520) become inf: the guard reports them; dZ cannot, whatever its size.
+// 0 keeps the f32 MFMA chain (tools/upd_micro.py variants).
 #ifndef DTUPD_X3
 #define DTUPD_X3 1
 #endif
@@ -162,6 +175,45 @@ __device__ __forceinline__ void hl_frag(const uint32_t (&w)[8], half8& h, half8&
   }
   h = __builtin_bit_cast(half8, uh);
   l = __builtin_bit_cast(half8, ul);
+}
+
+// The gradients' dZ operand (DTUPD_DZ_SCALE, the library default): upstream
+// gradients sit far below fp16's normal range (2^-14), where an unscaled
+// hi / lo pair keeps a few bits or none.  dZ is therefore multiplied by a
+// power of two that brings a group's largest |dZ| into [1, 2) before the
+// split, and the f32 accumulator rows of that group are multiplied by its
+// inverse at the end: both exact, so the split operands are the same bits
+// whatever power of two the loss carries.  The group is an output row of the
+// GEMM: for the weight gradient one output channel over the output rows a
+// workgroup takes (found in a pass over those dZ rows before the first is
+// staged), for the input gradient one input pixel and up to four of its taps
+// (their dZ over all 32 channels; conv4's 16 taps are four such groups, each
+// with its own pass through the accumulators).  Inside a group a dZ element d
+// is carried to max(2^-23 |d|, 2^-36 max|dZ|); include/dtupd.h states the
+// range.  0 keeps the unscaled split (the tests' revert check,
+// tools/upd_micro.py's noscale variant).  Batch 64, tools/upd_micro.py, us
+// with / without: weight gradient + reduce conv1 40.0 / 33.9 (the pass reads
+// dZ's 36 MB a second time), conv2 28.6 / 26.6, conv4 14.2 / 12.9; input
+// gradient conv2 27.5 / 27.8, conv3 12.2 / 11.8, conv4 13.5 / 10.9.
+#ifndef DTUPD_DZ_SCALE
+#define DTUPD_DZ_SCALE 1
+#endif
+__device__ __forceinline__ float absmax4(float m, float4 v) {
+  return fmaxf(fmaxf(fmaxf(m, fabsf(v.x)), fmaxf(fabsf(v.y), fabsf(v.z))), fabsf(v.w));
+}
+__device__ __forceinline__ float4 mul4(float4 v, float s) {
+  return make_float4(v.x * s, v.y * s, v.z * s, v.w * s);
+}
+// m = a group's max |dZ| (>= 0, never NaN: fmaxf drops them) -> 2^-e and 2^e
+// with e its exponent, clamped so that both are normal f32 (a zero or
+// subnormal group scales by 2^126, an infinite one stays infinite)
+struct Pow2 {
+  float scale, inv;
+};
+__device__ __forceinline__ Pow2 pow2_of(float m) {
+  uint32_t e = __float_as_uint(m) >> 23;
+  e = e < 1u ? 1u : (e > 253u ? 253u : e);
+  return Pow2{__uint_as_float((254u - e) << 23), __uint_as_float(e << 23)};
 }
 
 __device__ __forceinline__ f32x16 mfma4(float4 a, float4 b, f32x16 c) {
@@ -801,7 +853,16 @@ wgrad_kernel(int n, const float* __restrict__ x, const float* __restrict__ dz,
     if constexpr (X3) reinterpret_cast<uint4*>(xs[buf])[tid + i * NT] = hl4(v);
     else reinterpret_cast<float4*>(xs[buf])[tid + i * NT] = v;
   };
+  // x3: dZ scaled per output channel (DTUPD_DZ_SCALE above).  A thread's dZ
+  // float4s are always channels 4 (tid & 7) .. + 3 (NT and a row's floats
+  // are multiples of 32): dsc holds their scales, dmx every channel's max |dZ|
+  // over this workgroup's rows.
+  constexpr bool SC = X3 && DTUPD_DZ_SCALE != 0;
+  static_assert(!SC || (NT % 8 == 0 && DT % 32 == 0), "a thread keeps its channels");
+  __shared__ uint32_t dmx[SC ? 32 : 1];
+  float4 dsc = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
   auto putd = [&](int buf, int i, float4 v) __attribute__((always_inline)) {
+    if constexpr (SC) v = make_float4(v.x * dsc.x, v.y * dsc.y, v.z * dsc.z, v.w * dsc.w);
     if constexpr (X3) reinterpret_cast<uint4*>(ds[buf])[tid + i * NT] = hl4(v);
     else reinterpret_cast<float4*>(ds[buf])[tid + i * NT] = v;
   };
@@ -859,12 +920,38 @@ wgrad_kernel(int n, const float* __restrict__ x, const float* __restrict__ dz,
         acc[b] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, xb[xo + kr[b]], acc[b], 0, 0, 0);
     }
   };
+  if constexpr (DB)
+    if ((int)blockIdx.x < rows) DTUPD_FETCH((int)blockIdx.x);
+  if constexpr (SC) {
+    // one pass over this workgroup's dZ rows for the channels' max |dZ|
+    // (behind DB's first fetch; the rows come from L2 again when staged)
+    if (tid < 32) dmx[tid] = 0u;
+    __syncthreads();
+    float4 m = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll DTUPD_WG_PRE_UNROLL
+    for (int row = blockIdx.x; row < rows; row += gridDim.x) {
+      const float4* d = reinterpret_cast<const float4*>(dz + (size_t)row * DT) + tid;
+#pragma unroll
+      for (int i = 0; i < PD; ++i)
+        if (tid + i * NT < DT / 4) {
+          const float4 v = d[i * NT];
+          m = make_float4(fmaxf(m.x, fabsf(v.x)), fmaxf(m.y, fabsf(v.y)), fmaxf(m.z, fabsf(v.z)),
+                          fmaxf(m.w, fabsf(v.w)));
+        }
+    }
+    const int c0 = 4 * (tid & 7);   // non-negative floats order as their bits
+    atomicMax(&dmx[c0], __float_as_uint(m.x));
+    atomicMax(&dmx[c0 + 1], __float_as_uint(m.y));
+    atomicMax(&dmx[c0 + 2], __float_as_uint(m.z));
+    atomicMax(&dmx[c0 + 3], __float_as_uint(m.w));
+    __syncthreads();
+    dsc = make_float4(pow2_of(__uint_as_float(dmx[c0])).scale, pow2_of(__uint_as_float(dmx[c0 + 1])).scale,
+                      pow2_of(__uint_as_float(dmx[c0 + 2])).scale,
+                      pow2_of(__uint_as_float(dmx[c0 + 3])).scale);
+  }
   if constexpr (DB) {
     int buf = 0;
-    if ((int)blockIdx.x < rows) {
-      DTUPD_FETCH((int)blockIdx.x);
-      commit(0);
-    }
+    if ((int)blockIdx.x < rows) commit(0);
     __syncthreads();
     for (int row = blockIdx.x; row < rows; row += gridDim.x) {
       const int next = row + gridDim.x;
@@ -886,9 +973,14 @@ wgrad_kernel(int n, const float* __restrict__ x, const float* __restrict__ dz,
 #undef DTUPD_FETCH
   if constexpr (X3)
 #pragma unroll
-    for (int b = 0; b < NBW; ++b)
+    for (int r = 0; r < 16; ++r) {   // row co's scale undone
+      const float iv = SC ? pow2_of(__uint_as_float(dmx[SC ? acc_row(r, kk) : 0])).inv : 1.0f;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[b][r] += acc1[b][r] * kLoInv;
+      for (int b = 0; b < NBW; ++b) {
+        acc[b][r] += acc1[b][r] * kLoInv;
+        if constexpr (SC) acc[b][r] *= iv;
+      }
+    }
   // D[co][k]: lane (k = block * 32 + col), rows co
   float* pp = part + (size_t)blockIdx.x * 32 * G::K;
 #pragma unroll
@@ -1028,31 +1120,90 @@ dgrad_kernel(int n, const float* __restrict__ dz, const float* __restrict__ w,
       f32x16 acc1;
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc1[r] = 0.0f;
-#pragma unroll 2
-      for (int tap = 0; tap < D::TAPS; ++tap) {
+      struct A16 { float4 v[4]; };
+      auto load = [&](int tap) __attribute__((always_inline)) -> A16 {
         const int th = tap / D::T1, tw = tap - th * D::T1;
         const int oy = a - th, ox = b - tw;
         const bool ok = idx < np && oy >= 0 && oy < G::OH && ox >= 0 && ox < G::OW;
         const float4* src = reinterpret_cast<const float4*>(dzs + (ok ? (oy * G::OW + ox) * 32 : 0));
-        const int wtap = (ph + D::ST * th) * G::KS + pw + D::ST * tw;
-        float4 av[4];
+        A16 r;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          av[i] = src[(i >> 1) * 4 + (i & 1)];
-          if (!ok) av[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+          r.v[i] = src[(i >> 1) * 4 + (i & 1)];
+          if (!ok) r.v[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         }
+        return r;
+      };
+      auto mma = [&](int tap, const A16& av) __attribute__((always_inline)) {
+        const int th = tap / D::T1, tw = tap - th * D::T1;
+        const int wtap = (ph + D::ST * th) * G::KS + pw + D::ST * tw;
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
           half8 xh, xl;
-          split8(av[2 * u], av[2 * u + 1], xh, xl);
+          split8(av.v[2 * u], av.v[2 * u + 1], xh, xl);
           const half8 bh = wth[(wtap * 2 + u) * 64 + lane], bl = wtl[(wtap * 2 + u) * 64 + lane];
           acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh, bh, acc, 0, 0, 0);
           acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh, bl, acc1, 0, 0, 0);
           acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(xl, bh, acc1, 0, 0, 0);
         }
-      }
+      };
+      if constexpr (DTUPD_DZ_SCALE != 0) {
+        // dZ scaled per input pixel (DTUPD_DZ_SCALE above): a lane's A row is
+        // its pixel, so the row's max |dZ| is over the lane's values and its
+        // other half's (lane ^ 32).  The taps go in groups of kGT, loaded
+        // whole into registers before their MFMAs, each group with its own
+        // scale and its own pass through the accumulators (conv2, conv3: one
+        // group; conv4's 16 taps: four).
+        constexpr int kGT = D::TAPS < 4 ? D::TAPS : 4, kNG = D::TAPS / kGT;
+        static_assert(D::TAPS % kGT == 0, "whole groups");
+        f32x16 tot;
+        A16 hold[kGT], next[kGT];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] += acc1[r] * kLoInv;
+        for (int j = 0; j < kGT; ++j) hold[j] = load(j);
+#pragma unroll
+        for (int g = 0; g < kNG; ++g) {
+          // the next group's loads fly during this group's MFMAs (the
+          // clobbers keep the scheduler from hoisting every group's: 256
+          // registers of dZ for conv4)
+          if (g + 1 < kNG) {
+#pragma unroll
+            for (int j = 0; j < kGT; ++j) next[j] = load((g + 1) * kGT + j);
+            asm volatile("" ::: "memory");
+          }
+          float m = 0.0f;
+#pragma unroll
+          for (int j = 0; j < kGT; ++j)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) m = absmax4(m, hold[j].v[i]);
+          m = fmaxf(m, __shfl_xor(m, 32));
+          const Pow2 p = pow2_of(m);
+          if (g > 0)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = acc1[r] = 0.0f;
+#pragma unroll
+          for (int j = 0; j < kGT; ++j) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) hold[j].v[i] = mul4(hold[j].v[i], p.scale);
+            mma(g * kGT + j, hold[j]);
+          }
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {   // accumulator row = pixel acc_row(r, kk): lane of that index
+            const float v = (acc[r] + acc1[r] * kLoInv) * __shfl(p.inv, acc_row(r, kk));
+            tot[r] = g > 0 ? tot[r] + v : v;
+          }
+          if (g + 1 < kNG) {
+            asm volatile("" ::: "memory");
+#pragma unroll
+            for (int j = 0; j < kGT; ++j) hold[j] = next[j];
+          }
+        }
+        acc = tot;
+      } else {
+#pragma unroll 2
+        for (int tap = 0; tap < D::TAPS; ++tap) mma(tap, load(tap));
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] += acc1[r] * kLoInv;
+      }
     } else {
       const float* dzs = dz + (size_t)s * G::OPIX * 32 + 4 * kk;
 #pragma unroll 4

@@ -1,7 +1,7 @@
 /* dtupd.h — C-ABI of the DDPG update's convolutions (SURVEY.md §8f 1,
- * BASELINE configs[4]): hand-written f32 MFMA kernels for the conv_2d layers
- * of config.json's actor and critic (3 -> 32 8x8 stride 2; 32 -> 32 4x4
- * strides 2 and 1; padding 0, no dilation or groups), forward and both
+ * BASELINE configs[4]): hand-written MFMA kernels of f32 accuracy for the
+ * conv_2d layers of config.json's actor and critic (3 -> 32 8x8 stride 2;
+ * 32 -> 32 4x4 strides 2 and 1; padding 0, no dilation or groups), forward and both
  * gradients, in place of MIOpen (training/trainers.py:143-237 runs every
  * network in train mode through torch's conv2d and its autograd).
  *
@@ -11,9 +11,38 @@
  * OH = (IH - KS) / ST + 1, OW likewise.  Supported (C_in, KS, ST): (3, 8, 2),
  * (32, 4, 2), (32, 4, 1); DT_E_ARG otherwise.
  *
- * Numerics: v_mfma_f32_32x32x2_f32, an exact f32 fma chain per output over
- * its K products (the order differs from a CPU or MIOpen convolution, as
- * theirs differ from each other); no TF32-like rounding exists on gfx950.
+ * Numerics: float32 accuracy on fp16 MFMA ("x3", csrc/dtupd.hip DTUPD_X3) for
+ * dt_upd_conv_fwd*, dt_upd_conv_dgrad and dt_upd_conv_wgrad*, except the
+ * weight gradient of the 27 x 37 layer (OW = 17), which, like the
+ * dt_upd_linear_* kernels, is v_mfma_f32_32x32x2_f32: an exact f32 fma chain
+ * per output (the order differs from a CPU or MIOpen convolution, as theirs
+ * differ from each other).  x3 takes each f32 operand v as two fp16 values
+ * that together carry it to max(2^-23 |v|, 2^-36), multiplies with three
+ * fp16 MFMAs and accumulates in f32: |error| <= 2^-19 of the sum of the
+ * |products| of each output element (tests/test_gpu_upd_conv.py; observed
+ * below 2^-22) under these conditions on the operands:
+ *   x, w   used as they are: 2^-14 <= |v| < 65520 keeps f32 accuracy; smaller
+ *          values keep the absolute 2^-36 (enough beside operands of order
+ *          1: frames, BatchNorm outputs, weights), |v| >= 65520 becomes inf
+ *          (DT_GUARD_* reports the non-finite result downstream).
+ *   dz     any finite f32 magnitude, no overflow end: before the split it is
+ *          multiplied by the power of two that brings the largest |dz| of its
+ *          GROUP into [1, 2), and the group's f32 outputs are multiplied
+ *          back (both exact, so a gradient times 2^k gives the same bits
+ *          times 2^k).  A group is, for the weight gradient, one output
+ *          channel co over the output rows (sample, oy) one workgroup takes
+ *          (row r of a launch goes to workgroup r mod the grid; each dz
+ *          row its own workgroup up to 256 rows, 512 for C_in = 3, 128 for
+ *          OH <= 20); for the input gradient, one input pixel and the dz,
+ *          all 32 channels, of up to four of the (KS / ST)^2 output pixels
+ *          that reach it (stride 2: all four; stride 1: the four of one
+ *          output row, each output row its own group).
+ *          Inside a group dz elements within 2^14 of the largest keep f32
+ *          accuracy; smaller ones keep an absolute 2^-36 of the largest
+ *          (they vanish below 2^-37 of it), which is still within 2^-19 of
+ *          the output's sum of |products| unless the other operand is
+ *          ~2^-17 smaller at the large elements than at the small ones.
+ * No TF32-like rounding exists on gfx950.
  *
  * Conventions as dtsim.h: 0 or a negative DT_E_* code; device pointers; work
  * goes on `stream` (a hipStream_t).
