@@ -1,9 +1,10 @@
 // Observation path: build-defined 120x160 ego-centric top-down raster of the
 // lane markings fused with the features/line_detector1.py colour/edge filter
 // and PreliminaryTransformer's grey conversion.  render_kernel (below, "fused
-// render kernel") runs one 768-thread workgroup per environment and keeps the
-// frame in LDS (~71 KB: 4-pixel palette words + a 16-bit work image) until its
-// outputs are written: grey into the frame ring, four u8 masks.  Markings are
+// render kernel") runs one 512-thread workgroup per environment, four a CU, and
+// keeps the frame in LDS (< 40 KB: 4-pixel raster words + 16-bit work entries
+// of the words Canny has to look at) until its outputs are written: grey into
+// the frame ring, four u8 masks.  Markings are
 // Bresenham polylines (utils/bresenham.py semantics: both endpoints,
 // major-axis swap, D = 2dy - dx).  line_detect_kernel is the standalone
 // LineDetectorHSV on caller-supplied BGR images (dt_line_detect).
@@ -353,11 +354,15 @@ struct RenderArgs {
 //       non-uniform words get a slot (the list)
 //   2a  listed words: SWAR 3-channel Sobel -> entry (mag | dir); the slot + 1
 //       into the word's spare bits
-//   2b  listed words: Canny NMS + double threshold; weak pixels listed
+//   2b  listed words: Canny NMS + double threshold; weak pixels listed; and
+//       (dilation radius <= 1) the SWAR ellipse dilation of the word's colour
+//       bits from the 3 x 3 raster words around it, parked in its entries
 //   3   hysteresis over the weak list to a fixed point
-//   4   outputs: grey (float4 stores into the frame ring); masks: colour bits
-//       via a v_perm LUT, for quads with a listed word SWAR ellipse dilation
-//       and edge bits, 16 px per lane, four 16-B stores
+//   4   outputs: grey (float4 stores into the frame ring); masks, 16 px per
+//       lane, four 16-B stores: a listed word's colour and edge bytes from
+//       its entries, an unlisted word's colour bits via a v_perm LUT (its
+//       3 x 6-pixel neighbourhood is one colour: dilating changes nothing);
+//       radius 2-3 dilates every quad here instead (quad_masks, kBigR)
 // Slots past list_cap (a frame with more than kListCap non-uniform words:
 // never on the shipped maps) keep their entries in a per-env global spill
 // area; the workgroup then runs the phases' spill instantiation.
@@ -387,7 +392,14 @@ constexpr int kWeakCap = 512;
 constexpr int kSegRecs = 2176;     // uint2 segment records (phase 0, over the entry area)
 constexpr int kSpillHalves = 5 * NW;         // global spill per env: 4 entries + 1 list word
 enum { kNSpan = 0, kNSeg = 1, kNList = 2, kNQuad = 3, kNWeak = 4, kNCnt = 8 };
-constexpr uint16_t WK_MAG = 0x7FF, WK_DIR_SHIFT = 11, WK_CAND = 1 << 13, WK_EDGE = 1 << 14;
+// A work entry (16 bits a pixel of a listed word).  Sobel (2a) writes mag | dir;
+// NMS (2b) reads its own word's dir, then writes the entry back as
+//   mag (0-10) | dilated colour bits of the pixel (11-13) | CAND (14) | EDGE (15)
+// (neighbours' NMS reads only mag, which never changes; hysteresis reads and
+// sets only CAND / EDGE and writes the whole entry back).
+// (the dilated bits go in and out through dil_to_ent / ent_dil_bytes, EDGE out
+// through ent_edge_ff).
+constexpr uint16_t WK_MAG = 0x7FF, WK_DIR_SHIFT = 11, WK_CAND = 1 << 14, WK_EDGE = 1 << 15;
 
 struct RenderLds {
   uint32_t img[NW];   // raster bytes; from phase 2a a listed word's slot + 1 in bits 3-7
@@ -473,6 +485,30 @@ __device__ inline uint32_t shift_bytes(uint32_t prev, uint32_t cur, uint32_t nex
   if (d == 0) return cur;
   if (d > 0) return (cur >> (8 * d)) | (next << (32 - 8 * d));
   return (cur << (-8 * d)) | (prev >> (32 + 8 * d));
+}
+
+// The four work entries of a listed word (uint2, after NMS) as one byte a pixel:
+// EDGE (bit 15 of each entry) as 0 / 255 (v_perm selectors 8-11 replicate bit
+// 15 / 31 of a source dword over the byte) ...
+__device__ __forceinline__ uint32_t ent_edge_ff(uint2 v) {
+  return __builtin_amdgcn_perm(v.y, v.x, 0x0B0A0908u);
+}
+// ... the dilated colour bits (entry bits 11-13: bits 3-5 of its high byte) ...
+__device__ __forceinline__ uint32_t ent_dil_bytes(uint2 v) {
+  return (__builtin_amdgcn_perm(v.y, v.x, 0x07050301u) >> 3) & 0x07070707u;
+}
+// ... and the way in: colour-bit bytes (0..7) of pixels 0, 1 / 2, 3 at the
+// entries' bits 11-13
+__device__ __forceinline__ uint2 dil_to_ent(uint32_t dil) {
+  return make_uint2(__builtin_amdgcn_perm(0u, dil, 0x010C000Cu) << 3,
+                    __builtin_amdgcn_perm(0u, dil, 0x030C020Cu) << 3);
+}
+// colour-bit bytes (0..7) -> the 0 / 255 bytes of colour plane k: the byte is
+// the selector into an 8-entry LUT of constants (one v_perm a plane)
+__device__ __forceinline__ uint32_t plane_ff(uint32_t cb, int k) {
+  return k == 0   ? __builtin_amdgcn_perm(0xFF00FF00u, 0xFF00FF00u, cb)
+         : k == 1 ? __builtin_amdgcn_perm(0xFFFF0000u, 0xFFFF0000u, cb)
+                  : __builtin_amdgcn_perm(0xFFFFFFFFu, 0u, cb);
 }
 
 __device__ inline int lane_prefix(uint64_t m) {
@@ -750,8 +786,7 @@ __device__ __forceinline__ void quad_masks(const RenderLds& S, const Slots<kSpil
   for (int j = 0; j < 4; ++j) {
     const int s = slot1_of(ow[j]);
     const uint2 v = s ? sl.ent4(s - 1) : make_uint2(0u, 0u);
-    // the high byte of each 16-bit entry (v_perm), EDGE = its bit 6
-    edg[j] = (__builtin_amdgcn_perm(v.y, v.x, 0x07050301u) >> 6) & 0x01010101u;
+    edg[j] = ent_edge_ff(v);
   }
   uint32_t o[4][4];
 #pragma unroll
@@ -759,7 +794,7 @@ __device__ __forceinline__ void quad_masks(const RenderLds& S, const Slots<kSpil
     o[0][j] = bytes01_to_ff(dil[j] & 0x01010101u);
     o[1][j] = bytes01_to_ff((dil[j] >> 1) & 0x01010101u);
     o[2][j] = bytes01_to_ff((dil[j] >> 2) & 0x01010101u);
-    o[3][j] = bytes01_to_ff(edg[j]);
+    o[3][j] = edg[j];
   }
   const int p0 = r * W + 4 * cw0;
 #pragma unroll
@@ -767,8 +802,10 @@ __device__ __forceinline__ void quad_masks(const RenderLds& S, const Slots<kSpil
     *reinterpret_cast<uint4*>(mb + k * NPIX + p0) = make_uint4(o[k][0], o[k][1], o[k][2], o[k][3]);
 }
 
-// Phases 2a-3 (Sobel, NMS, hysteresis) on the listed words.
-template <bool kSpill>
+// Phases 2a-3 (Sobel, NMS, hysteresis) on the listed words.  With a dilation
+// radius <= 1 (!kBigR) NMS also dilates the listed words' colour bits, into
+// their entries: the output phase then only unpacks them.
+template <bool kSpill, bool kBigR>
 __device__ __forceinline__ void canny(const RenderArgs& a, RenderLds& S, int e,
                                                 int nlist) {
   const int tid = opaque_tid();
@@ -818,7 +855,15 @@ __device__ __forceinline__ void canny(const RenderArgs& a, RenderLds& S, int e,
   // phase 2b: NMS + double threshold on the listed words, branch-free: the
   // entries of the 3 x 3 word neighbourhood are read once (0 outside the
   // image and for unlisted words: their Sobel is 0), each pixel's two
-  // neighbours selected by its direction class
+  // neighbours selected by its direction class.
+  // ... and the dilation of the word's colour bits (radius <= 1): the raster
+  // words of the same neighbourhood, read for the slot lookups anyway, as
+  // colour-bit bytes (v_perm LUT; 0 outside the image), OR-ed over the
+  // structuring element's offsets (scalar tests, one v_alignbyte a shift).
+  // Only listed words need it: an unlisted word's 3 x 6 pixels are one colour,
+  // so its dilation is its own colour bits.
+  const uint32_t blo = S.bits_lo, bhi = S.bits_hi;
+  const uint64_t dmask = L.dil_mask;
   constexpr int U = 1;
   for (int s0 = 0; s0 < nlist; s0 += U * T) {
     if (s0 + (tid & ~63) >= nlist) break;   // wave-uniform: nothing left for this wave
@@ -834,32 +879,55 @@ __device__ __forceinline__ void canny(const RenderArgs& a, RenderLds& S, int e,
       const int w = sl.word(sc);
       const int r = w / WPR, cw = w - r * WPR, c0 = 4 * cw;
       const uint2 cur = sl.ent4(sc);
-      uint2 nb[3][3];
+      // magnitudes of the 3 x 6 pixel block around the word (a side word gives
+      // one pixel: a 16-bit read), and the colour-bit bytes of its words (!kBigR)
+      uint32_t M[3][6], cb[3][3];
 #pragma unroll
       for (int dy = -1; dy <= 1; ++dy) {
 #pragma unroll
         for (int dx = -1; dx <= 1; ++dx) {
-          if (dy == 0 && dx == 0) {
-            nb[1][1] = cur;
-            continue;
-          }
+          const int k = dy + 1;
           const int rr = r + dy, cc = cw + dx;
-          const bool in = (unsigned)rr < (unsigned)H && (unsigned)cc < (unsigned)WPR;
-          const int slot = slot1_of(S.img[in ? rr * WPR + cc : w]);
-          const uint2 v = sl.ent4(slot > 0 ? slot - 1 : 0);
-          nb[dy + 1][dx + 1] = (in && slot > 0) ? v : make_uint2(0u, 0u);
+          const bool own = dy == 0 && dx == 0;
+          const bool in = own || ((unsigned)rr < (unsigned)H && (unsigned)cc < (unsigned)WPR);
+          const uint32_t rw = S.img[in ? rr * WPR + cc : w];
+          if (!kBigR) cb[k][dx + 1] = in ? __builtin_amdgcn_perm(bhi, blo, rw & kPalMask) : 0u;
+          const int slot = slot1_of(rw);
+          const bool has = in && slot > 0;
+          const int sn = slot > 0 ? slot - 1 : 0;
+          if (dx == 0) {
+            const uint2 v = own ? cur : sl.ent4(sn);
+            const uint32_t vx = has ? v.x : 0u, vy = has ? v.y : 0u;
+            M[k][1] = vx & WK_MAG;
+            M[k][2] = (vx >> 16) & WK_MAG;
+            M[k][3] = vy & WK_MAG;
+            M[k][4] = (vy >> 16) & WK_MAG;
+          } else {
+            const uint32_t v = sl.ent(sn, dx < 0 ? 3 : 0);
+            M[k][dx < 0 ? 0 : 5] = has ? v & WK_MAG : 0u;
+          }
         }
       }
-      // magnitudes of the 3 x 6 pixel block around the word
-      uint32_t M[3][6];
+      uint32_t dil = 0u;
+      if (!kBigR) {
+        const auto tap = [&](int dy, int dx) {   // uniform
+          return ((dmask >> ((dy + 3) * 7 + (dx + 3))) & 1ull) != 0ull;
+        };
+        // the own row and column first, then the corners under one test of
+        // their own: the 3 x 3 ellipse, the default, is a cross, and skips
+        // the corner words' LUT reads and shifts with that branch
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        M[k][0] = (nb[k][0].y >> 16) & WK_MAG;
-        M[k][1] = nb[k][1].x & WK_MAG;
-        M[k][2] = (nb[k][1].x >> 16) & WK_MAG;
-        M[k][3] = nb[k][1].y & WK_MAG;
-        M[k][4] = (nb[k][1].y >> 16) & WK_MAG;
-        M[k][5] = nb[k][2].x & WK_MAG;
+        for (int dx = -1; dx <= 1; ++dx)
+          if (tap(0, dx)) dil |= shift_bytes(cb[1][0], cb[1][1], cb[1][2], dx);
+        if (tap(-1, 0)) dil |= cb[0][1];
+        if (tap(1, 0)) dil |= cb[2][1];
+        if (tap(-1, -1) || tap(-1, 1) || tap(1, -1) || tap(1, 1)) {
+#pragma unroll
+          for (int dy = -1; dy <= 1; dy += 2)
+#pragma unroll
+            for (int dx = -1; dx <= 1; dx += 2)
+              if (tap(dy, dx)) dil |= shift_bytes(cb[dy + 1][0], cb[dy + 1][1], cb[dy + 1][2], dx);
+        }
       }
       const uint32_t vv[4] = {cur.x & 0xFFFFu, cur.x >> 16, cur.y & 0xFFFFu, cur.y >> 16};
       uint32_t setb[4];
@@ -883,9 +951,13 @@ __device__ __forceinline__ void canny(const RenderArgs& a, RenderLds& S, int e,
         wk[4 * u + i] = (uint16_t)(r * W + c0 + i);
       }
       // only this lane writes these four entries; neighbours read only the
-      // magnitude bits, which do not change
-      upd[u] = (setb[0] | setb[1] | setb[2] | setb[3]) != 0u;
-      nv[u] = make_uint2(cur.x | setb[0] | (setb[1] << 16), cur.y | setb[2] | (setb[3] << 16));
+      // magnitude bits, which do not change.  dir is dead from here: its
+      // bits and bit 13 take the dilated colour bits (0 with kBigR: unused)
+      constexpr uint32_t kMag2 = WK_MAG | ((uint32_t)WK_MAG << 16);
+      const uint2 de = dil_to_ent(dil);
+      upd[u] = act;
+      nv[u] = make_uint2((cur.x & kMag2) | de.x | setb[0] | (setb[1] << 16),
+                         (cur.y & kMag2) | de.y | setb[2] | (setb[3] << 16));
     }
 #pragma unroll
     for (int u = 0; u < U; ++u)
@@ -944,8 +1016,9 @@ __device__ __forceinline__ void canny(const RenderArgs& a, RenderLds& S, int e,
 // four 1-KB wave instructions (lane l of store j writes word 64 j + l of the
 // wave's run).  Masks: a lane per quad, consecutive lanes consecutive 16-B
 // pieces of each plane, so every line of a plane is written whole by one
-// instruction: a quad without a listed word (and radius <= 1) takes its own
-// colour bits, the others the dilation + edge path.
+// instruction.  Radius <= 1: every word unpacks what NMS left in its entries
+// (listed) or takes its own colour bits (unlisted), no neighbour is read;
+// radius 2-3 (kBigR): the dilation + edge path quad_masks.
 // kIdx: the frame goes out as palette bytes (a.index) instead of grey floats
 // (a.gray): two instantiations, so the grey path keeps its register budget.
 template <bool kSpill, bool kIdx, bool kBigR>
@@ -969,8 +1042,9 @@ __device__ __forceinline__ void write_outputs(const RenderArgs& a, RenderLds& S,
   float* gbase = !kIdx && a.gray && !dead ? a.gray + (size_t)e * a.slots * NPIX : nullptr;
   uint8_t* ibase = kIdx && !dead ? a.index + (size_t)e * a.slots * NPIX : nullptr;
   const uint32_t blo = S.bits_lo, bhi = S.bits_hi;
-  const bool quick_masks = L.dil_r <= 1;
   const int lane = tid & 63;
+  // not unrolled: three copies of the body spill SGPRs and reload them here
+#pragma unroll 1
   for (int q0 = 0; q0 < NQ; q0 += T) {
     const int wbase = 4 * (q0 + (tid - lane));
     if (gbase || ibase) {
@@ -1008,38 +1082,45 @@ __device__ __forceinline__ void write_outputs(const RenderArgs& a, RenderLds& S,
     const int q = q0 + tid;
     if (q < NQ) {
       if (mbase) {
-        const uint4 m = *reinterpret_cast<const uint4*>(S.img + 4 * q);
-        // a quad without a listed word (and radius <= 1) is its own colour bits,
-        // and the dilation path gives it the same bytes: so a wave takes the
-        // quick path only when all its quads may, else every lane the dilation
-        // path (a wave of 64 quads spans six rows and usually holds a listed
-        // word: running both paths under divergence cost both)
-        const bool uni = quick_masks && ((m.x | m.y | m.z | m.w) & ~kPalMask) == 0u;
-        if (__ballot(!uni) == 0) {   // wave-uniform
-          const uint32_t mw[4] = {m.x, m.y, m.z, m.w};
-          uint32_t o[3][4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const uint32_t cb = __builtin_amdgcn_perm(bhi, blo, mw[j]);
-            o[0][j] = bytes01_to_ff(cb & 0x01010101u);
-            o[1][j] = bytes01_to_ff((cb >> 1) & 0x01010101u);
-            o[2][j] = bytes01_to_ff((cb >> 2) & 0x01010101u);
-          }
-#pragma unroll
-          for (int k = 0; k < 3; ++k)
-            *reinterpret_cast<uint4*>(mbase + k * NPIX + 16 * q) =
-                make_uint4(o[k][0], o[k][1], o[k][2], o[k][3]);
-          *reinterpret_cast<uint4*>(mbase + 3 * NPIX + 16 * q) = make_uint4(0u, 0u, 0u, 0u);
-        } else {
+        if (kBigR) {
           // radius 2-3 (kernel sizes 5, 7) in their own kernel: their
           // unrolled ellipses held 450 SGPR spills in every instantiation
-          if (kBigR) {
-            if (L.dil_r == 2) quad_masks<2>(S, sl, L, mbase, q);
-            else quad_masks<3>(S, sl, L, mbase, q);
-          } else {
-            if (L.dil_r == 0) quad_masks<0>(S, sl, L, mbase, q);
-            else quad_masks<1>(S, sl, L, mbase, q);
+          if (L.dil_r == 2) quad_masks<2>(S, sl, L, mbase, q);
+          else quad_masks<3>(S, sl, L, mbase, q);
+        } else {
+          // radius <= 1, one path for every quad: a listed word's dilated
+          // colour bits and edges are in its entries (NMS put them there); an
+          // unlisted word is one colour with its whole 3 x 6-pixel
+          // neighbourhood, so its dilation is its own colour bits (v_perm
+          // LUT) and it has no edge
+          const uint4 m = *reinterpret_cast<const uint4*>(S.img + 4 * q);
+          const uint32_t mw[4] = {m.x, m.y, m.z, m.w};
+          uint32_t o[4][4];
+          int sj[4];
+          uint2 vj[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {   // the four entry reads in flight together
+            sj[j] = slot1_of(mw[j]);
+            vj[j] = sl.ent4(sj[j] > 0 ? sj[j] - 1 : 0);
           }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int s = sj[j];
+            const uint2 v = vj[j];
+            // (unmasked: an unlisted word has no slot bits, a listed one's is not used)
+            const uint32_t own = __builtin_amdgcn_perm(bhi, blo, mw[j]);
+            // selected with an all-ones mask: as a ?: of the two expressions the
+            // compiler branches per word and waits for each LDS read in turn
+            const uint32_t lm = s > 0 ? ~0u : 0u;
+            const uint32_t cb = (ent_dil_bytes(v) & lm) | (own & ~lm);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) o[k][j] = plane_ff(cb, k);
+            o[3][j] = ent_edge_ff(v) & lm;
+          }
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            *reinterpret_cast<uint4*>(mbase + k * NPIX + 16 * q) =
+                make_uint4(o[k][0], o[k][1], o[k][2], o[k][3]);
         }
       }
       if (a.rgb) {
@@ -1331,9 +1412,10 @@ __device__ __forceinline__ void render_env(const RenderArgs& a, RenderLds& S, in
 
   // phase 1: per 16-pixel quad (4 words of a row): the 3 x 6-word neighbourhood
   // decides each word's uniformity exactly (all 18 pixels around it one
-  // byte).  Non-uniform words get a slot (the list); a quad with one takes
-  // the dilation path of the output phase (every quad does when the dilation
-  // radius is >= 2: uniformity only covers +-1 pixel).
+  // byte).  Non-uniform words get a slot (the list): Canny and, for a
+  // dilation radius <= 1, the dilation run on those alone (a uniform word has
+  // Sobel 0 and dilates to itself; uniformity only covers +-1 pixel, so
+  // radius >= 2 dilates every quad in the output phase).
   uint8_t* const mb0 = half == 0 ? a.masks : (half == 1 ? a.masks2 : a.masks3);
   uint8_t* mbase = mb0 ? mb0 + (size_t)e * 4 * NPIX : nullptr;
   constexpr int kQuadPer = (NQ + T - 1) / T;  // quads per lane (3 at 512 threads)
@@ -1408,12 +1490,12 @@ __device__ __forceinline__ void render_env(const RenderArgs& a, RenderLds& S, in
   // phases 2-3, then the outputs
   const int nlist = C[kNList];
   if (nlist <= a.list_cap) {
-    if (mbase) canny<false>(a, S, e, nlist);
+    if (mbase) canny<false, kBigR>(a, S, e, nlist);
     RENT(13);
     RENDER_STOP(4);
     write_outputs<false, kIdx, kBigR>(a, S, e, mbase, half);
   } else {
-    if (mbase) canny<true>(a, S, e, nlist);
+    if (mbase) canny<true, kBigR>(a, S, e, nlist);
     RENT(13);
     RENDER_STOP(4);
     write_outputs<true, kIdx, kBigR>(a, S, e, mbase, half);
@@ -2019,14 +2101,21 @@ static int render_launch(dt_handle* h, const dt_render_io* io, const dt_render_i
     cap = hipStreamCaptureStatusNone;
   a.sched = h->n > kSchedTail && cap == hipStreamCaptureStatusNone
                 ? (uint32_t*)h->render_sched : nullptr;
-  if (a.sched) {
+  if (a.sched && h->render_pending && (hipStream_t)stream != h->render_stream) {
+    // the stream changed: this launch waits for what the last one's stream
+    // holds now (that launch included).  The event is recorded here, not
+    // after every launch: launches that stay on one stream, the usual case,
+    // put no marker behind the kernel and do no event work at all.
     if (!h->render_done)
-      // ordering on this device only: no system-scope fence (with one, the
-      // record after every launch cost the config-3 bench 2 % of its rate)
+      // ordering on this device only: no system-scope fence
       HIP_OR_FAIL(h, hipEventCreateWithFlags(&h->render_done,
                                              hipEventDisableTiming | hipEventDisableSystemFence));
-    if (h->render_pending && (hipStream_t)stream != h->render_stream)
+    if (hipEventRecord(h->render_done, h->render_stream) == hipSuccess) {
       HIP_OR_FAIL(h, hipStreamWaitEvent((hipStream_t)stream, h->render_done, 0));
+    } else {
+      (void)hipGetLastError();   // e.g. that stream was destroyed: wait for the device
+      HIP_OR_FAIL(h, hipDeviceSynchronize());
+    }
   }
   a.launch = h->render_launches++;
 #endif
@@ -2057,7 +2146,6 @@ static int render_launch(dt_handle* h, const dt_render_io* io, const dt_render_i
     return DT_E_HIP;
   }
   if (a.sched) {
-    HIP_OR_FAIL(h, hipEventRecord(h->render_done, (hipStream_t)stream));
     h->render_stream = (hipStream_t)stream;
     h->render_pending = true;
   }
