@@ -52,6 +52,44 @@ __device__ __forceinline__ void leaky4(float4 v, float4 b, float slope, float (&
 #pragma unroll
   for (int k = 0; k < 4; ++k) x[k] = x[k] > 0.0f ? x[k] : x[k] * slope;
 }
+// the same, and pos = z + bias > 0: the branch LeakyReLU's derivative takes.
+// The activation's sign is not the pre-activation's for a negative slope.
+__device__ __forceinline__ void leaky4(float4 v, float4 b, float slope, float (&x)[4],
+                                       bool (&pos)[4]) {
+  x[0] = v.x + b.x;
+  x[1] = v.y + b.y;
+  x[2] = v.z + b.z;
+  x[3] = v.w + b.w;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    pos[k] = x[k] > 0.0f;
+    x[k] = pos[k] ? x[k] : x[k] * slope;
+  }
+}
+
+// The kFin (32) partials a channel in red2 -> one, in the 32 threads
+// tid = 16 * channel: pairs 16 apart, then a butterfly over 16 lanes.  Five
+// levels, not a chain of 32: every merge rounds the running mean, and in a
+// chain those roundings add up to about an ulp of the mean (|mean| >> std:
+// tests/test_gpu_bn_tail.py holds the mean to 4 * 2^-24 (|mean| + std)); in a
+// tree the early ones average out.  The order is fixed by index.
+__device__ __forceinline__ bool merge_fin(const float (&red2)[kFin][C][3], int& ch, float& cn,
+                                          float& cm, float& cm2) {
+  const int tid = threadIdx.x;
+  if (tid >= 16 * C) return false;   // waves 0-7 whole
+  const int j = tid & 15;
+  ch = tid >> 4;
+  cn = red2[j][ch][0];
+  cm = red2[j][ch][1];
+  cm2 = red2[j][ch][2];
+  chan(cn, cm, cm2, red2[j + 16][ch][0], red2[j + 16][ch][1], red2[j + 16][ch][2]);
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) {
+    const float bn = __shfl_xor(cn, o, 16), bm = __shfl_xor(cm, o, 16), bq = __shfl_xor(cm2, o, 16);
+    chan(cn, cm, cm2, bn, bm, bq);
+  }
+  return j == 0;
+}
 
 // ---- forward 1: a = leaky(z + bias) and the batch statistics of a --------------------
 __global__ void __launch_bounds__(kT)
@@ -86,7 +124,7 @@ bn_stats_kernel(int64_t m, const float* __restrict__ z, const float* __restrict_
   }
   __syncthreads();
   float* part = work;   // [grid][C][3]
-  // 128 slots a channel: kFin threads a channel merge 4 each, then one thread
+  // 128 slots a channel: kFin threads a channel merge 4 each, then a tree (merge_fin)
   __shared__ float red2[kFin][C][3];
   {
     const int ch = tid & (C - 1), j = tid / C;
@@ -97,18 +135,20 @@ bn_stats_kernel(int64_t m, const float* __restrict__ z, const float* __restrict_
     red2[j][ch][2] = cm2;
   }
   __syncthreads();
-  if (tid < C) {
-    float cn = 0.0f, cm = 0.0f, cm2 = 0.0f;
-    for (int s = 0; s < kFin; ++s) chan(cn, cm, cm2, red2[s][tid][0], red2[s][tid][1], red2[s][tid][2]);
-    float* p = part + ((size_t)blockIdx.x * C + tid) * 3;
-    st_wt(p, cn);
-    st_wt(p + 1, cm);
-    st_wt(p + 2, cm2);
+  {
+    int ch;
+    float cn, cm, cm2;
+    if (merge_fin(red2, ch, cn, cm, cm2)) {
+      float* p = part + ((size_t)blockIdx.x * C + ch) * 3;
+      st_wt(p, cn);
+      st_wt(p + 1, cm);
+      st_wt(p + 2, cm2);
+    }
   }
   unsigned int* counters = reinterpret_cast<unsigned int*>(work + (size_t)kMaxGrid * C * 3);
   if (!last_arrival(&counters[0])) return;
   acquire_partials();
-  // the last workgroup: kFin threads a channel over the partials, then one
+  // the last workgroup: kFin threads a channel over the partials, then the tree
   {
     const int ch = tid & (C - 1), j = tid / C;
     float cn = 0.0f, cm = 0.0f, cm2 = 0.0f;
@@ -136,13 +176,13 @@ bn_stats_kernel(int64_t m, const float* __restrict__ z, const float* __restrict_
     red2[j][ch][2] = cm2;
   }
   __syncthreads();
-  if (tid < C) {
-    float cn = 0.0f, cm = 0.0f, cm2 = 0.0f;
-    for (int s = 0; s < kFin; ++s) chan(cn, cm, cm2, red2[s][tid][0], red2[s][tid][1], red2[s][tid][2]);
+  int ch;
+  float cn, cm, cm2;
+  if (merge_fin(red2, ch, cn, cm, cm2)) {
     const float var = cm2 / cn;                       // biased: the normalisation
     const float invstd = 1.0f / sqrtf(var + eps);
-    mean_invstd[tid] = cm;
-    mean_invstd[C + tid] = invstd;
+    mean_invstd[ch] = cm;
+    mean_invstd[C + ch] = invstd;
     // the merged count is every pixel exactly (float integers up to 2^24)
     const bool lost = m < (int64_t(1) << 24) ? cn != (float)m
                                               : fabsf(cn - (float)m) > 1e-6f * (float)m;
@@ -151,14 +191,14 @@ bn_stats_kernel(int64_t m, const float* __restrict__ z, const float* __restrict_
     const float unbiased = cn > 1.0f ? cm2 / (cn - 1.0f) : var;
     // one running-statistics update per reference forward over this batch
     // (the same batch statistics each time: a shared trunk, trainer.py)
-    float rm = running_mean[tid], rv = running_var[tid];
+    float rm = running_mean[ch], rv = running_var[ch];
     for (int u = 0; u < updates; ++u) {
       rm = (1.0f - momentum) * rm + momentum * cm;
       rv = (1.0f - momentum) * rv + momentum * unbiased;
     }
-    running_mean[tid] = rm;
-    running_var[tid] = rv;
-    if (tid == 0 && nbt) nbt[0] += updates;
+    running_mean[ch] = rm;
+    running_var[ch] = rv;
+    if (ch == 0 && nbt) nbt[0] += updates;
   }
 }
 
@@ -309,13 +349,14 @@ bn_bwd_apply_kernel(int64_t m, const float* __restrict__ dy, const float* __rest
     const float4 g4 = ld4(dy, q);
     const float g[4] = {g4.x, g4.y, g4.z, g4.w};
     float x[4];
-    leaky4(ld4(z, q), b, slope, x);
+    bool pos[4];
+    leaky4(ld4(z, q), b, slope, x, pos);
     float o[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const float xh = (x[k] - mu[k]) * is[k];
       const float da = k1[k] * (g[k] - k2[k] - xh * k3[k]);
-      o[k] = x[k] > 0.0f ? da : da * slope;
+      o[k] = pos[k] ? da : da * slope;
       acc[0][k] += o[k];
     }
     st4(dz, q, make_float4(o[0], o[1], o[2], o[3]));

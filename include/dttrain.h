@@ -83,7 +83,8 @@ int dt_bn_leaky_apply(int64_t m, const float* z, const float* bias, float slope,
  * z and bias (a = leaky_relu(z + bias, slope) recomputed):
  *   dgamma = sum(dy * xhat), dbeta = sum(dy), xhat = (a - mean) * invstd;
  *   da = gamma * invstd * (dy - dbeta / m - xhat * dgamma / m);
- *   dz = a > 0 ? da : slope * da  (LeakyReLU's backward: a > 0 iff z + bias > 0);
+ *   dz = z + bias > 0 ? da : slope * da  (LeakyReLU's backward, from the sign of
+ *        the pre-activation: a's sign is not z + bias's for a negative slope);
  *   dbias = sum(dz).
  *   dz            device f32 [m, 32] out
  *   dbias, dgamma, dbeta  device f32 [32] out (overwritten) */

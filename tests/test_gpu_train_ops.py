@@ -94,6 +94,45 @@ def test_networks_with_and_without_fused_tail(gpu, kind):
             assert torch.equal(b, c), name
 
 
+def test_network_with_negative_slope_on_every_fused_path(gpu):
+    """conv -> LeakyReLU(-0.2) -> BatchNorm blocks, for which the activation's
+    sign is not the pre-activation's, one per path into dt_bn_leaky_bwd: a
+    geometry outside UPD_CONV_LAYERS (_BnLeaky), one block of it alone
+    (_ConvBnLeaky) and a chain of two (_ConvTrunk), batch 4: output, every
+    parameter gradient and the buffers match torch's modules."""
+    from aido1_amd.actor import _Conv, _Seq
+    torch.manual_seed(6)
+
+    def block(cin, k, s):
+        return [_Conv(cin, 32, k, s), nn.LeakyReLU(-0.2), nn.BatchNorm2d(32)]
+    net = _Seq(block(3, 4, 2) + block(32, 4, 2) + [nn.Identity()] + block(32, 4, 2)
+               + block(32, 4, 1))
+    net = net.to(gpu).to(memory_format=torch.channels_last).train()
+    ref = copy.deepcopy(net)
+    x = torch.rand(4, 3, 116, 156, device=gpu).contiguous(memory_format=torch.channels_last)
+    try:
+        _Seq.fused_tail = False
+        out_ref = ref(x)
+        out_ref.square().mean().backward()
+    finally:
+        _Seq.fused_tail = True
+    out = net(x)
+    out.square().mean().backward()
+    bns = [m for m in net.modules() if isinstance(m, nn.BatchNorm2d)]
+    assert hasattr(bns[0], '_dt_work_fwd') and hasattr(bns[1], '_dt_work_upd')
+    assert hasattr(bns[2], '_dt_part') and hasattr(bns[3], '_dt_part')
+    assert not any(hasattr(m, '_dt_work_bwd') for m in ref.modules())
+    torch.testing.assert_close(out, out_ref, rtol=1e-4, atol=1e-5)
+    for (name, p), (_, q) in zip(net.named_parameters(), ref.named_parameters()):
+        scale = q.grad.abs().max().item()
+        assert (p.grad - q.grad).abs().max().item() <= 2e-4 * scale + 1e-7, name
+    for (name, b), (_, c) in zip(net.named_buffers(), ref.named_buffers()):
+        if b.dtype.is_floating_point:
+            torch.testing.assert_close(b, c, rtol=1e-5, atol=1e-6, msg=name)
+        else:
+            assert torch.equal(b, c), name
+
+
 def test_device_adam_matches_torch_adam(gpu):
     """dt_adam (one launch over every parameter) against torch.optim.Adam
     (plain, Python-double bias corrections) over five steps with a changing
