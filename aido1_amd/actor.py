@@ -23,10 +23,13 @@ BatchNorms into the following conv / linear.  The linears run as torch fp16
 GEMMs (hipBLASLt) and the head in dt_actor_head.
 """
 import copy
+import ctypes
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from aido1_amd import _lib
 
 FLAT = 32 * 9 * 14  # 4032 (120x160 input)
 
@@ -326,13 +329,28 @@ def apply_head(x, head, max_action=1.0):
 
 
 class FusedActor(nn.Module):
-    """Inference copy of an actor for the batched rollout, weights in `dtype`
-    (fp16 by default in the rollout: under per-sample normalisation bf16's
-    8-bit mantissa costs ~5e-2 in the actions vs ~6e-3 for fp16 on rendered
-    frames, tools/actor_precision.py; both run on MFMA at the same rate), convolutions channels_last (MIOpen's NHWC bf16 kernels are
-    ~1.75x its NCHW ones on these shapes, tools/actor_micro.py), the first
-    conv's input channels re-ordered per call so it reads the frame ring in
-    place.  Two modes:
+    """Inference copy of an actor for the batched rollout, weights in `dtype`;
+    the first conv's input channels follow the frame ring's slot order, so
+    the ring is read in place.  Three paths from frames to actions, chosen
+    by `dtype`, `mode` and the input:
+
+    * x3 -- ``dtype=torch.float32, mode='reference'``, the rollout's default
+      (rollout.ActorRollout): the convolutions and the head at float32
+      accuracy on fp16 MFMA (dt_conv1x_split, dt_conv32x_split,
+      dt_actor_head_x3_drop; include/dtactor.h), |da| <= 1e-4 against the
+      float64 actor on rendered frames (tests/test_gpu_actor_x3.py);
+    * fp16 -- ``dtype=torch.float16``, either mode, the fast mode: fp16 MFMA
+      with float32 accumulation (dt_conv1_split / dt_conv1_index_split,
+      dt_conv32_split, dt_actor_head_f16_drop), ~1e-2 on the same frames
+      (tests/test_gpu_actor.py);
+    * torch -- every other dtype (the constructor's bf16 default among them),
+      the CPU, and an input that is not the frame ring: channels_last
+      library convolutions (MIOpen's NHWC kernels are ~1.75x its NCHW ones on
+      these shapes, tools/actor_micro.py), dt_sample_norm and torch linears;
+      under per-sample normalisation bf16 costs ~5e-2 in the actions
+      (tools/actor_precision.py).
+
+    Two modes:
 
     * ``'reference'`` — what the reference's explorers compute: every model is
       in train mode (managers.py:264-268, explorers.py:46) and acts on a batch
@@ -344,9 +362,8 @@ class FusedActor(nn.Module):
       next conv / the first linear: the checkpoint-evaluation policy
       (test-ddpg-cnn.py, DDPG.act after .eval()).
 
-    Numerically within bf16 rounding of the float32 modules
-    (tests/test_gpu_actor.py).  ``refresh(actor)`` re-derives the weights in
-    place (the acting copy follows the trainer's target actor)."""
+    ``refresh(actor)`` re-derives the weights in place (the acting copy
+    follows the trainer's target actor)."""
 
     def __init__(self, actor, dtype=torch.bfloat16, mode='eval'):
         super().__init__()
@@ -401,12 +418,14 @@ class FusedActor(nn.Module):
     @torch.no_grad()
     def refresh(self, actor, graph=None):
         """Re-derive the acting weights from `actor`'s current ones, in place.
-        On the GPU the ~12 copy / gather kernels of a refresh are captured into
-        a HIP graph at the first refresh from a given source (its parameters'
-        addresses) and replayed afterwards: the training loop refreshes both
-        acting copies after every update, and issued one by one from Python
-        the kernels left the GPU idle ~0.4 ms a decision (launch gaps).
-        graph=False forces the eager path."""
+        On the GPU a reference-mode refresh of the HIP chains is one
+        dt_refresh_copy launch (_refresh_gather); any other one's ~12 copy /
+        gather kernels are captured into a HIP graph at the first refresh
+        from a given source (its parameters' addresses) and replayed
+        afterwards: the training loop refreshes both acting copies after
+        every update, and issued one by one from Python the kernels left the
+        GPU idle ~0.4 ms a decision (launch gaps).  graph=False forces the
+        eager path (_refresh)."""
         dev = self.w0frag.device
         if graph is None:
             graph = dev.type == 'cuda'
@@ -414,15 +433,8 @@ class FusedActor(nn.Module):
             return self._refresh(actor)
         if self.mode == 'reference' and (self.dtype == torch.float16 or self.x3):
             return self._refresh_gather(actor)
-        # the source's tensors are listed once per source module (walking the
-        # module tree costs ~80 us of host time a call); their addresses are
-        # checked on every call, so a source whose storage moved is recaptured
-        srcs = self.__dict__.setdefault('_refresh_srcs', {})
-        ts = srcs.get(id(actor))
-        if ts is None or ts[0] is not actor:
-            ts = srcs[id(actor)] = (actor, list(actor.parameters()) + list(actor.buffers()))
-        key = (id(actor),) + tuple(t.data_ptr() for t in ts[1])
         cache = self.__dict__.setdefault('_refresh_graphs', {})
+        key = self._source_key(actor)
         g = cache.get(key)
         if g is None:
             self._refresh(actor)                 # eager once: lazily built index maps, pools
@@ -432,41 +444,54 @@ class FusedActor(nn.Module):
             cache[key] = g
         g.replay()
 
+    def _source_key(self, actor):
+        """The key of the refresh caches: the source module and its tensors'
+        addresses.  The tensors are listed once per source (walking the
+        module tree costs ~80 us of host time a call); their addresses are
+        checked on every call, so a source whose storage moved is captured
+        again."""
+        srcs = self.__dict__.setdefault('_refresh_srcs', {})
+        ts = srcs.get(id(actor))
+        if ts is None or ts[0] is not actor:
+            ts = srcs[id(actor)] = (actor, list(actor.parameters()) + list(actor.buffers()))
+        return (id(actor),) + tuple(t.data_ptr() for t in ts[1])
+
+    def _index_map(self, kind):
+        """The fragment layout `kind` ('conv1', 'conv32', 'head') as flat
+        indices into the layer's weights, -1 for conv1's zero padding
+        channel; built once a device."""
+        key = (kind, self.w0frag.device)
+        maps = self.__dict__.setdefault('_index_maps', {})
+        if key not in maps:
+            m = {'conv1': conv1_fragment_index, 'conv32': conv32_fragment_index,
+                 'head': head_fragment_index}[kind](key[1])
+            maps[key] = torch.where(m < 32 * 3 * 64, m, -1) if kind == 'conv1' else m
+        return maps[key]
+
     def _refresh_pairs(self, actor):
-        """(destination, source, logical index map or None, kind) of a
-        reference-mode refresh: what _refresh copies, with the fragment
-        gathers' index maps; kind 2 = the x3 (hi, lo) pair into dst[0], dst[1]
-        (dt_refresh_copy), None = by the destination's dtype."""
+        """What a reference-mode refresh copies, stated once: (destination,
+        source, index map or None, kind).  A map gathers the source's logical
+        elements into an MFMA fragment layout (-1: zero); kind 2 = the x3
+        (hi, lo) halves into dst[0], dst[1], None = by the destination's
+        dtype.  _refresh executes the pairs with torch, _refresh_gather
+        compiles them into dt_refresh_copy's table."""
         convs, bns, lin1, lin2 = actor.layers()
         pairs = [(d, sp, None, None) for d, sp in zip(
             list(self.w) + list(self.b) + list(self.gamma) + list(self.beta) +
             [self.w1, self.b1, self.w2, self.b2],
             [c.weight for c in convs] + [c.bias for c in convs] + [bn.weight for bn in bns] +
             [bn.bias for bn in bns] + [lin1.weight, lin1.bias, lin2.weight, lin2.bias])]
-        dev = self.w0frag.device
-        if getattr(self, '_fidx', None) is None or self._fidx[0].device != dev:
-            self._fidx = (conv1_fragment_index(dev), conv32_fragment_index(dev))
-            self._w0pad = torch.zeros(32 * 3 * 64 + 1, device=dev)
-        n0 = convs[0].weight.numel()
-        f0 = self._fidx[0].reshape(-1)
-        f0 = torch.where(f0 < n0, f0, torch.full_like(f0, -1))
-        pairs.append((self.w0frag, convs[0].weight, f0, None))
-        for i in range(1, 4):
-            pairs.append((self.wfrag[i - 1], convs[i].weight, self._fidx[1].reshape(-1), None))
+        m1, m32 = self._index_map('conv1'), self._index_map('conv32')
+        pairs.append((self.w0frag, convs[0].weight, m1, None))
+        pairs += [(self.wfrag[i - 1], convs[i].weight, m32, None) for i in range(1, 4)]
         if self.x3:   # the x3 chain's fragments
-            pairs.append((self.w0x, convs[0].weight, f0, 2))
-            for i in range(1, 4):
-                pairs.append((self.wx32[i - 1], convs[i].weight, self._fidx[1].reshape(-1), None))
+            pairs.append((self.w0x, convs[0].weight, m1, 2))
+            pairs += [(self.wx32[i - 1], convs[i].weight, m32, None) for i in range(1, 4)]
             if hasattr(self, 'w1x'):
-                if getattr(self, '_h1idx', None) is None or self._h1idx.device != dev:
-                    self._h1idx = head_fragment_index(dev)
-                pairs.append((self.w1x, lin1.weight, self._h1idx, 2))
+                pairs.append((self.w1x, lin1.weight, self._index_map('head'), 2))
         if hasattr(self, 'w1f'):   # the fp16 head's fragments (from float32: fp16 rounding)
-            if getattr(self, '_h1idx', None) is None or self._h1idx.device != dev:
-                self._h1idx = head_fragment_index(dev)
-            pairs.append((self.w1f, lin1.weight, self._h1idx, None))
-        for i in range(4):
-            pairs.append((self.bf[i], convs[i].bias, None, None))
+            pairs.append((self.w1f, lin1.weight, self._index_map('head'), None))
+        pairs += [(self.bf[i], convs[i].bias, None, None) for i in range(4)]
         return pairs
 
     @staticmethod
@@ -491,25 +516,18 @@ class FusedActor(nn.Module):
         return torch.where(lg >= 0, src_phys[lg.clamp(min=0)], lg)
 
     def _refresh_gather(self, actor):
-        """A reference-mode fp16 refresh as ONE dt_refresh_copy launch
+        """A reference-mode refresh (fp16 or x3) as ONE dt_refresh_copy launch
         (include/dtactor.h): every acting tensor gathered and converted from
         the source's float32 parameters through index maps built at the first
         refresh from a source (its tensors' addresses are checked every call).
         Issued as ~28 small kernels (or their graph) it cost ~0.19 ms of GPU
         time a decision in the training loop."""
-        import ctypes
-        from aido1_amd import _lib
-        srcs = self.__dict__.setdefault('_refresh_srcs', {})
-        ts = srcs.get(id(actor))
-        if ts is None or ts[0] is not actor:
-            ts = srcs[id(actor)] = (actor, list(actor.parameters()) + list(actor.buffers()))
-        key = (id(actor),) + tuple(t.data_ptr() for t in ts[1])
         cache = self.__dict__.setdefault('_refresh_tables', {})
+        key = self._source_key(actor)
         ent = cache.get(key)
         if ent is None:
-            pairs = self._refresh_pairs(actor)
             keep, rows = [], []
-            for dst, src, lg, kind in pairs:
+            for dst, src, lg, kind in self._refresh_pairs(actor):
                 if src.dtype != torch.float32 or dst.dtype not in (torch.float16, torch.float32):
                     raise ValueError('refresh: float32 sources, fp16 / f32 destinations')
                 if kind == 2 and not (dst.is_contiguous() and dst.dtype == torch.float16):
@@ -534,74 +552,64 @@ class FusedActor(nn.Module):
             raise _lib.DtError('dt_refresh_copy failed (%d)' % rc)
 
     def _refresh(self, actor):
-        convs, bns, lin1, lin2 = actor.layers()
+        """The eager refresh: reference mode executes _refresh_pairs with
+        torch; eval mode folds each BatchNorm's running statistics into the
+        next layer in float64."""
         if self.mode == 'reference':
-            ws = [c.weight for c in convs]
-            bs = [c.bias for c in convs]
-            copy_grouped(
-                list(self.w) + list(self.b) + list(self.gamma) + list(self.beta) +
-                [self.w1, self.b1, self.w2, self.b2],
-                ws + bs + [bn.weight for bn in bns] + [bn.bias for bn in bns] +
-                [lin1.weight, lin1.bias, lin2.weight, lin2.bias])
-            if hasattr(self, 'w1x'):
-                if getattr(self, '_h1idx', None) is None or self._h1idx.device != self.w1.device:
-                    self._h1idx = head_fragment_index(self.w1.device)
-                self.w1x.view(2, -1).copy_(split_hl(torch.take(self.w1, self._h1idx)))
-        else:
-            scale = shift = None
-            ws, bs = [], []
-            for i, (conv, bn) in enumerate(zip(convs, bns)):
-                w = conv.weight.detach().double()
-                b = conv.bias.detach().double()
-                if scale is not None:   # fold previous BN: conv(s*x + t)
-                    b = b + (w * shift.view(1, -1, 1, 1)).sum((1, 2, 3))
-                    w = w * scale.view(1, -1, 1, 1)
-                self.w[i].copy_(w)
-                self.b[i].copy_(b)
-                ws.append(w)
-                bs.append(b)
-                scale = bn.weight.detach().double() / torch.sqrt(
-                    bn.running_var.detach().double() + bn.eps)
-                shift = bn.bias.detach().double() - bn.running_mean.detach().double() * scale
-            w1 = lin1.weight.detach().double()
-            b1 = lin1.bias.detach().double()
-            s_flat = scale.repeat_interleave(FLAT // scale.numel())
-            t_flat = shift.repeat_interleave(FLAT // shift.numel())
-            self.w1.copy_(w1 * s_flat.view(1, -1))
-            self.b1.copy_(b1 + w1 @ t_flat)
-            self.w2.copy_(lin2.weight)
-            self.b2.copy_(lin2.bias)
-        if hasattr(self, 'w1f'):   # from the acting w1 (folded in eval mode)
-            if getattr(self, '_h1idx', None) is None or self._h1idx.device != self.w1.device:
-                self._h1idx = head_fragment_index(self.w1.device)
-            self.w1f.view(-1).copy_(torch.take(self.w1, self._h1idx))
+            pairs = self._refresh_pairs(actor)
+            plain = [p for p in pairs if p[2] is None]
+            copy_grouped([p[0] for p in plain], [p[1] for p in plain])
+            for dst, src, lg, kind in pairs:
+                if lg is not None:
+                    v = _take(src, lg)
+                    if kind == 2:
+                        dst.view(2, -1).copy_(split_hl(v.float()))
+                    else:
+                        dst.view(-1).copy_(v)
+            return
+        convs, bns, lin1, lin2 = actor.layers()
+        scale = shift = None
+        ws, bs = [], []
+        for i, (conv, bn) in enumerate(zip(convs, bns)):
+            w = conv.weight.detach().double()
+            b = conv.bias.detach().double()
+            if scale is not None:   # fold previous BN: conv(s*x + t)
+                b = b + (w * shift.view(1, -1, 1, 1)).sum((1, 2, 3))
+                w = w * scale.view(1, -1, 1, 1)
+            self.w[i].copy_(w)
+            self.b[i].copy_(b)
+            ws.append(w)
+            bs.append(b)
+            scale = bn.weight.detach().double() / torch.sqrt(
+                bn.running_var.detach().double() + bn.eps)
+            shift = bn.bias.detach().double() - bn.running_mean.detach().double() * scale
+        w1 = lin1.weight.detach().double()
+        b1 = lin1.bias.detach().double()
+        s_flat = scale.repeat_interleave(FLAT // scale.numel())
+        t_flat = shift.repeat_interleave(FLAT // shift.numel())
+        self.w1.copy_(w1 * s_flat.view(1, -1))
+        self.b1.copy_(b1 + w1 @ t_flat)
+        self.w2.copy_(lin2.weight)
+        self.b2.copy_(lin2.bias)
+        if hasattr(self, 'w1f'):   # from the acting (folded) w1
+            self.w1f.view(-1).copy_(torch.take(self.w1, self._index_map('head')))
         self._fragments(ws, bs)
 
     def _fragments(self, ws, bs):
-        """The MFMA A fragments (fp16) and f32 biases of the four convs for
-        dt_conv1 / dt_conv32, from weights of any float dtype and memory
-        format: one gather a layer through index maps built once (the layouts
-        of conv1_fragments / conv32_fragments)."""
-        dev = self.w0frag.device
-        if getattr(self, '_fidx', None) is None or self._fidx[0].device != dev:
-            self._fidx = (conv1_fragment_index(dev), conv32_fragment_index(dev))
-            self._w0pad = torch.zeros(32 * 3 * 64 + 1, device=dev)   # + the zero channel's slot
-        self._w0pad[:-1].view(32, 3, 8, 8).copy_(ws[0])
-        self.w0frag.view(-1).copy_(torch.take(self._w0pad, self._fidx[0]))
+        """Eval mode's MFMA A fragments (fp16) and f32 biases of the four
+        convs for dt_conv1 / dt_conv32, from the folded float64 weights: one
+        gather a layer through the index maps (the layouts of
+        conv1_fragments / conv32_fragments)."""
+        self.w0frag.view(-1).copy_(_take(ws[0].float(), self._index_map('conv1')))
         for i in range(1, 4):
-            self.wfrag[i - 1].view(-1).copy_(torch.take(ws[i], self._fidx[1]))
+            self.wfrag[i - 1].view(-1).copy_(torch.take(ws[i], self._index_map('conv32')))
         torch._foreach_copy_(list(self.bf.unbind(0)), list(bs))
-        if self.x3:
-            self.w0x.view(2, -1).copy_(split_hl(torch.take(self._w0pad, self._fidx[0])))
-            for i in range(1, 4):
-                self.wx32[i - 1].view(-1).copy_(torch.take(ws[i], self._fidx[1]))
 
     def _lrelu_sample_norm(self, x, i):
         """LeakyReLU then BatchNorm2d in train mode on a batch of one, for every
         sample at once: the dt_sample_norm HIP kernel (include/dtactor.h) on
         the GPU, in place; a two-pass torch restatement on CPU (tests)."""
         if x.is_cuda:
-            from aido1_amd import _lib
             n, c, h, w = x.shape
             assert x.is_contiguous(memory_format=torch.channels_last)
             dt = {torch.bfloat16: 0, torch.float32: 1, torch.float16: 2}[x.dtype]
@@ -620,242 +628,241 @@ class FusedActor(nn.Module):
         b = self.beta[i].view(1, -1, 1, 1)
         return ((x - mean) / torch.sqrt(var + self.eps[i]) * g + b).to(self.dtype)
 
-    def _convs_hip(self, ring, order):
-        """The four convolutions by the hand-written MFMA kernels (include/dtactor.h):
-        dt_conv1 straight from the ring (grey f32, or palette-index u8 through
-        dt_conv1_index_split), then dt_conv32 x3; in reference
-        mode every per-sample BatchNorm is applied by the next kernel while it
-        stages its input (the last one in conv4's epilogue).  Returns the
-        flattened [N, 4032] fp16 activation in NCHW order."""
-        from aido1_amd import _lib
-        L = _lib.lib()
-        n, slots = ring.shape[0], ring.shape[1]
-        dev = ring.device
-        flat = torch.empty(n, FLAT, dtype=torch.float16, device=dev)
-        rc = self._convs(L, ring, slots, order, flat, self._conv_buffers(n, dev))
-        if rc != 0:
-            raise _lib.DtError('dt_conv1 / dt_conv32 failed (%d)' % rc)
-        return flat
+    def _ring_ok(self, x):
+        """x is the frame ring the HIP chains take: on the GPU, grey float32
+        or palette-index uint8, contiguous [n, >= 3 slots, 120, 160], for a
+        32 x 3 x 8 x 8 conv1."""
+        return (x.is_cuda and x.dtype in (torch.float32, torch.uint8) and x.is_contiguous() and
+                tuple(x.shape[2:]) == (120, 160) and x.shape[1] >= 3 and
+                self.w[0].shape == (32, 3, 8, 8))
 
-    def _conv_buffers(self, n, dev):
-        """The intermediate activations (fp16 NHWC) and, in reference mode, the
-        per-sample BatchNorm statistics [n, 32, 3] of conv1..conv3 (mean of the
-        stored centred values, M2, centre: include/dtactor.h)."""
+    def _chain_buffers(self, n, dev):
+        """The activations between the convolutions, each in the layout its
+        consumer reads -- the fp16 chain's fp16 NHWC, the x3 chain's HLB
+        ((hi, lo) fp16 pairs, include/dtactor.h; read at stride 2, 2, 1) and
+        its f32 flattened conv4 output -- and in reference mode the
+        per-sample BatchNorm statistics [n, 32, 3] of conv1..conv3 (mean of
+        the stored centred values, M2, centre)."""
         key = (n, dev, self.mode)
         if getattr(self, '_bufs_key', None) != key:
-            f16 = torch.float16
-            ref = self.mode == 'reference'
-            self._bufs = {
-                'y1': torch.empty(n, 57, 77, 32, dtype=f16, device=dev),
-                'y2': torch.empty(n, 27, 37, 32, dtype=f16, device=dev),
-                'y3': torch.empty(n, 12, 17, 32, dtype=f16, device=dev),
-                'p1': torch.empty(n, 32, 3, device=dev) if ref else None,
-                'p2': torch.empty(n, 32, 3, device=dev) if ref else None,
-                'p3': torch.empty(n, 32, 3, device=dev) if ref else None}
-            self._bufs_key = key
+            B = {}
+            # conv1..conv3's output: height, width, and the stride it is read at
+            for i, (h, w, stride) in enumerate(((57, 77, 2), (27, 37, 2), (12, 17, 1)), 1):
+                B['y%d' % i] = torch.empty(hlb_shape(n, h, w, stride) if self.x3 else (n, h, w, 32),
+                                           dtype=torch.float16, device=dev)
+                B['p%d' % i] = torch.empty(n, 32, 3, device=dev) \
+                    if self.mode == 'reference' else None
+            if self.x3:
+                B['flat'] = torch.empty(n, FLAT, device=dev)
+            self._bufs, self._bufs_key = B, key
         return self._bufs
 
-    def _convs(self, L, ring, slots, order, flat, B):
-        import ctypes
-        n = ring.shape[0]
-        ref = self.mode == 'reference'
+    def _convs(self, ring, order, other=None, n0=None):
+        """The four convolutions by the hand-written MFMA kernels
+        (include/dtactor.h) straight from the ring (grey f32 or palette-index
+        u8): conv1, then the three 32 -> 32 layers, one launch each, in fp16
+        (dt_conv1_split / dt_conv1_index_split, dt_conv32_split) or at float32
+        accuracy (x3: dt_conv1x_split, dt_conv32x_split).  In reference mode
+        every per-sample BatchNorm is applied by the next kernel, the last one
+        in conv4's epilogue; eval mode passes no statistics.  With `other`,
+        samples [n0, n) use its weights in the same launches: the persistent
+        workgroups are split between the two sets.  Returns the flattened
+        [n, 4032] activation in NCHW order: the fp16 chain a freshly allocated
+        fp16 tensor, the x3 chain float32 in its buffers' own memory, valid
+        until the next call."""
+        L = _lib.lib()
+        n, slots = ring.shape[0], ring.shape[1]
+        index = ring.dtype == torch.uint8
+        ref = self.mode == 'reference'       # x3 exists only in reference mode
+        B = self._chain_buffers(n, ring.device)
+        if self.x3:
+            conv1, frames = L.dt_conv1x_split, (ring.data_ptr(), int(index))
+            conv32, w0, wl, flat = L.dt_conv32x_split, 'w0x', 'wx32', B['flat']
+        else:
+            conv1 = L.dt_conv1_index_split if index else L.dt_conv1_split
+            frames = (ring.data_ptr(),)
+            conv32, w0, wl = L.dt_conv32_split, 'w0frag', 'wfrag'
+            flat = torch.empty(n, FLAT, dtype=torch.float16, device=ring.device)
         stream = torch.cuda.current_stream(ring.device).cuda_stream
         ptr = (lambda t: t.data_ptr() if t is not None else None)
         o = (ctypes.c_int32 * 3)(*[int(v) for v in order])
-        conv1 = L.dt_conv1_index_split if ring.dtype == torch.uint8 else L.dt_conv1_split
-        rc = conv1(ring.data_ptr(), n, slots, o, self.w0frag.data_ptr(), self.bf[0].data_ptr(),
-                   None, B['y1'].data_ptr(), ptr(B['p1']), 0.01, stream)
-        ins = [(B['y1'], B['p1']), (B['y2'], B['p2']), (B['y3'], B['p3'])]
-        outs = [(B['y2'], B['p2']), (B['y3'], B['p3']), (flat, None)]
+
+        def weights(a, layer):
+            """a's fragments, bias, input norm and output norm of conv
+            layer + 2, in dt_conv_set's order."""
+            last = ref and layer == 2
+            return (getattr(a, wl)[layer].data_ptr(), a.bf[layer + 1].data_ptr(),
+                    a.gamma[layer].data_ptr() if ref else None,
+                    a.beta[layer].data_ptr() if ref else None,
+                    a.gamma[3].data_ptr() if last else None,
+                    a.beta[3].data_ptr() if last else None)
+
+        set2 = None if other is None else ctypes.byref(_lib.DtConvSet(
+            n0, getattr(other, w0).data_ptr(), other.bf[0].data_ptr()))
+        rc = conv1(*frames, n, slots, o, getattr(self, w0).data_ptr(), self.bf[0].data_ptr(), set2,
+                   B['y1'].data_ptr(), ptr(B['p1']), 0.01, stream)
+        acts = [(B['y1'], B['p1']), (B['y2'], B['p2']), (B['y3'], B['p3']), (flat, None)]
         for layer in range(3):
             if rc != 0:
                 break
-            x, pp = ins[layer]
-            y, po = outs[layer]
-            last = layer == 2
-            rc = L.dt_conv32(
-                layer + 2, n, x.data_ptr(), self.wfrag[layer].data_ptr(),
-                self.bf[layer + 1].data_ptr(), ptr(pp),
-                self.gamma[layer].data_ptr() if ref else None,
-                self.beta[layer].data_ptr() if ref else None, self.eps[layer] if ref else 0.0,
-                y.data_ptr(), ptr(po),
-                self.gamma[3].data_ptr() if (ref and last) else None,
-                self.beta[3].data_ptr() if (ref and last) else None,
-                self.eps[3] if ref else 0.0, 0.01, stream)
-        return rc
-
-    def _x3_input(self, x):
-        """x is a frame ring the float32-accurate HIP chain takes."""
-        return (self.x3 and x.is_cuda and x.dtype in (torch.float32, torch.uint8) and
-                x.is_contiguous() and tuple(x.shape[2:]) == (120, 160) and x.shape[1] >= 3 and
-                self.w[0].shape == (32, 3, 8, 8))
-
-    def _x3_buffers(self, n, dev):
-        """The HLB activations ((hi, lo) fp16 pairs, include/dtactor.h) of
-        conv1..conv3, their per-sample statistics [n, 32, 3] and the f32
-        flattened conv4 output."""
-        key = (n, dev)
-        if getattr(self, '_xbufs_key', None) != key:
-            f16 = torch.float16
-            self._xbufs = {   # each in the layout its consumer reads (stride 2, 2, 1)
-                'y1': torch.empty(hlb_shape(n, 57, 77, 2), dtype=f16, device=dev),
-                'y2': torch.empty(hlb_shape(n, 27, 37, 2), dtype=f16, device=dev),
-                'y3': torch.empty(hlb_shape(n, 12, 17, 1), dtype=f16, device=dev),
-                'p1': torch.empty(n, 32, 3, device=dev),
-                'p2': torch.empty(n, 32, 3, device=dev),
-                'p3': torch.empty(n, 32, 3, device=dev),
-                'flat': torch.empty(n, FLAT, device=dev)}
-            self._xbufs_key = key
-        return self._xbufs
-
-    def _convs_x3(self, ring, order, other=None, n0=None):
-        """The four convolutions at float32 accuracy (dt_conv1x_split, then
-        dt_conv32x_split x3; include/dtactor.h): every per-sample BatchNorm is
-        folded into the next layer's weights, the last one applied in conv4's
-        epilogue.  With `other`, samples [n0, n) use its weights in the same
-        launches.  Returns the flattened [N, 4032] float32 activation (NCHW
-        order); it is the buffers' own memory, valid until the next call."""
-        import ctypes
-        from aido1_amd import _lib
-        L = _lib.lib()
-        n, slots = ring.shape[0], ring.shape[1]
-        B = self._x3_buffers(n, ring.device)
-        stream = torch.cuda.current_stream(ring.device).cuda_stream
-        o = (ctypes.c_int32 * 3)(*[int(v) for v in order])
-        s1 = None if other is None else ctypes.byref(_lib.DtConvSet(
-            n0, other.w0x.data_ptr(), other.bf[0].data_ptr()))
-        rc = L.dt_conv1x_split(ring.data_ptr(), 1 if ring.dtype == torch.uint8 else 0, n, slots,
-                               o, self.w0x.data_ptr(), self.bf[0].data_ptr(), s1,
-                               B['y1'].data_ptr(), B['p1'].data_ptr(), 0.01, stream)
-        ins = [(B['y1'], B['p1']), (B['y2'], B['p2']), (B['y3'], B['p3'])]
-        outs = [(B['y2'], B['p2']), (B['y3'], B['p3']), (B['flat'], None)]
-        for layer in range(3):
-            if rc != 0:
-                break
-            x, pp = ins[layer]
-            y, po = outs[layer]
-            last = layer == 2
-            s2 = None
-            if other is not None:
-                s2 = ctypes.byref(_lib.DtConvSet(
-                    n0, other.wx32[layer].data_ptr(), other.bf[layer + 1].data_ptr(),
-                    other.gamma[layer].data_ptr(), other.beta[layer].data_ptr(),
-                    other.gamma[3].data_ptr() if last else None,
-                    other.beta[3].data_ptr() if last else None))
-            rc = L.dt_conv32x_split(
-                layer + 2, n, x.data_ptr(), self.wx32[layer].data_ptr(),
-                self.bf[layer + 1].data_ptr(), pp.data_ptr(), self.gamma[layer].data_ptr(),
-                self.beta[layer].data_ptr(), self.eps[layer], y.data_ptr(),
-                po.data_ptr() if po is not None else None,
-                self.gamma[3].data_ptr() if last else None,
-                self.beta[3].data_ptr() if last else None, self.eps[3], 0.01, s2, stream)
+            (x, pp), (y, po) = acts[layer], acts[layer + 1]
+            w, b, in_gamma, in_beta, out_gamma, out_beta = weights(self, layer)
+            set2 = None if other is None else ctypes.byref(_lib.DtConvSet(
+                n0, *weights(other, layer)))
+            rc = conv32(layer + 2, n, x.data_ptr(), w, b, ptr(pp), in_gamma, in_beta,
+                        self.eps[layer] if ref else 0.0, y.data_ptr(), ptr(po), out_gamma,
+                        out_beta, self.eps[3] if ref else 0.0, 0.01, set2, stream)
         if rc != 0:
-            raise _lib.DtError('dt_conv1x_split / dt_conv32x_split failed (%d)' % rc)
-        return B['flat']
+            raise _lib.DtError('%s / %s failed (%d)' % (conv1.__name__, conv32.__name__, rc))
+        return flat
+
+    def _convs_torch(self, x, order):
+        """The trunk by library convolutions (channels_last) for every dtype
+        and device, from a stack or a ring of frames: the flattened [N, 4032]
+        activation in `dtype`."""
+        from aido1_amd.render import as_gray
+        x = as_gray(x)
+        w0 = self.w[0]
+        if order is not None:
+            inv = sorted(range(len(order)), key=lambda c: order[c])
+            w0 = w0[:, inv].contiguous(memory_format=torch.channels_last)
+        x = x.to(self.dtype, memory_format=torch.channels_last)
+        # MIOpen's heuristic choice for conv2 at these shapes is a 2.5 ms CK
+        # kernel; its benchmark-mode search finds a 0.57 ms one (once per shape)
+        with torch.backends.cudnn.flags(enabled=True, benchmark=True,
+                                        deterministic=False, allow_tf32=False):
+            for i in range(4):
+                x = F.conv2d(x, w0 if i == 0 else self.w[i], self.b[i], stride=self.strides[i])
+                x = self._lrelu_sample_norm(x, i) if self.mode == 'reference' else F.leaky_relu(x)
+        # flatten in NCHW order, as the reference's view(x.size(0), -1)
+        return x.contiguous().flatten(1)
 
     def _pairable(self, other, x):
-        if other is None or other.mode != self.mode or not x.is_cuda:
-            return False
-        if self.x3 and other.x3:
-            return self._x3_input(x) and other.w[0].shape == (32, 3, 8, 8)
-        return (self.dtype == torch.float16 and other.dtype == torch.float16 and
-                x.dtype in (torch.float32, torch.uint8) and x.is_contiguous() and
-                tuple(x.shape[2:]) == (120, 160) and x.shape[1] >= 3 and
-                self.w[0].shape == (32, 3, 8, 8) and other.w[0].shape == (32, 3, 8, 8))
+        """`other` can share this actor's launches on x: the same mode, the
+        same HIP chain, the ring."""
+        return (other is not None and other.mode == self.mode and
+                ((self.x3 and other.x3) or self.dtype == other.dtype == torch.float16) and
+                self._ring_ok(x) and other._ring_ok(x))
+
+    @torch.no_grad()
+    def forward(self, x, order=None):
+        """x: [N,3,120,160] stack (oldest first), or the frame ring with
+        `order` = ring slots oldest->newest (RenderOutput.order()); grey
+        float32 or palette-index uint8 frames (render.py)."""
+        return self._act(x, order)
 
     @torch.no_grad()
     def forward_pair(self, other, x, order, n0, out=None):
         """The samples [0, n0) through this actor and [n0, n) through `other`
         (the exploiting explorers' copy, rollout.ActorRollout) with ONE launch
-        per convolution: dt_conv1_split / dt_conv32_split split the persistent
-        workgroups between the two weight sets (include/dtactor.h).  Returns
-        [n, 2] (into `out` if given); each row equals the forward of its own
-        actor."""
+        per convolution and one head (_convs, _heads).  Returns [n, 2] (into
+        `out` if given); each row equals the forward of its own actor.  An
+        `other` that cannot share the launches, or n0 at an end: each actor
+        acts on its own rows."""
         n = x.shape[0]
+        if self._pairable(other, x) and 0 < n0 < n:
+            return self._act(x, order, other, n0, out)
         if out is None:
             out = torch.empty(n, 2, dtype=torch.float32, device=x.device)
-        if not self._pairable(other, x) or not 0 < n0 < n:
-            out[:n0] = self(x[:n0], order)
-            out[n0:] = other(x[n0:], order)
-            return out
-        if self.x3:
-            flat = self._convs_x3(x, order, other, n0)
-            if self._head_x3_ok(flat, other):
-                return self._heads_x3(other, flat, n0, out)
-            out[:n0] = self._head(flat[:n0])
-            out[n0:] = other._head(flat[n0:])
-            return out
-        flat = self._convs_pair(other, x, order, n0)
-        if self._head_fusable(other):
-            return self._heads(other, flat, n0, out)
-        for a, sl in ((self, slice(0, n0)), (other, slice(n0, n))):
-            out[sl] = a._head(flat[sl])
+        out[:n0] = self(x[:n0], order)
+        out[n0:] = other(x[n0:], order)
         return out
 
+    def _act(self, x, order, other=None, n0=None, out=None):
+        """The one route from frames to actions: the HIP chain of this
+        actor's dtype on the ring (the product paths), else the torch
+        convolutions; then _heads."""
+        if (self.x3 or self.dtype == torch.float16) and self._ring_ok(x):
+            flat = self._convs(x, order if order is not None else [0, 1, 2], other, n0)
+        else:
+            flat = self._convs_torch(x, order)
+        return self._heads(other, flat, n0, out)
+
+    # the split forms of the chain under the names of its three former copies
+    # (tests/test_gpu_actor.py, tests/test_gpu_actor_x3.py)
+    _convs_hip = _convs_x3 = _convs
+
     def _convs_pair(self, other, x, order, n0):
-        """_convs_hip over both weight sets: the flattened [n, 4032] fp16
-        activations, rows [0, n0) from this actor's weights, the rest from
-        `other`'s."""
-        import ctypes
-        from aido1_amd import _lib
-        L = _lib.lib()
-        n = x.shape[0]
-        ref = self.mode == 'reference'
-        flat = torch.empty(n, FLAT, dtype=torch.float16, device=x.device)
-        B = self._conv_buffers(n, x.device)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        ptr = (lambda t: t.data_ptr() if t is not None else None)
-        o = (ctypes.c_int32 * 3)(*[int(v) for v in order])
-        s1 = _lib.DtConvSet(n0, other.w0frag.data_ptr(), other.bf[0].data_ptr())
-        conv1 = L.dt_conv1_index_split if x.dtype == torch.uint8 else L.dt_conv1_split
-        rc = conv1(x.data_ptr(), n, x.shape[1], o, self.w0frag.data_ptr(), self.bf[0].data_ptr(),
-                   ctypes.byref(s1), B['y1'].data_ptr(), ptr(B['p1']), 0.01, stream)
-        ins = [(B['y1'], B['p1']), (B['y2'], B['p2']), (B['y3'], B['p3'])]
-        outs = [(B['y2'], B['p2']), (B['y3'], B['p3']), (flat, None)]
-        for layer in range(3):
-            if rc != 0:
-                break
-            xi, pp = ins[layer]
-            y, po = outs[layer]
-            last = layer == 2
-            s2 = _lib.DtConvSet(n0, other.wfrag[layer].data_ptr(), other.bf[layer + 1].data_ptr(),
-                                ptr(other.gamma[layer]) if ref else None,
-                                ptr(other.beta[layer]) if ref else None,
-                                ptr(other.gamma[3]) if (ref and last) else None,
-                                ptr(other.beta[3]) if (ref and last) else None)
-            rc = L.dt_conv32_split(
-                layer + 2, n, xi.data_ptr(), self.wfrag[layer].data_ptr(),
-                self.bf[layer + 1].data_ptr(), ptr(pp),
-                self.gamma[layer].data_ptr() if ref else None,
-                self.beta[layer].data_ptr() if ref else None, self.eps[layer] if ref else 0.0,
-                y.data_ptr(), ptr(po),
-                self.gamma[3].data_ptr() if (ref and last) else None,
-                self.beta[3].data_ptr() if (ref and last) else None,
-                self.eps[3] if ref else 0.0, 0.01, ctypes.byref(s2), stream)
-        if rc != 0:
-            raise _lib.DtError('dt_conv1_split / dt_conv32_split failed (%d)' % rc)
-        return flat
+        return self._convs(x, order, other, n0)
 
     _HEAD_CODES = {'none': 0, 'tanh': 1, 'sigmoid': 2}
 
     def _head_fusable(self, other=None):
+        """The actors' fp16 heads fit one dt_actor_head launch."""
         nets = [self] if other is None else [self, other]
         return all(a.dtype == torch.float16 and a.w2.is_cuda and a.w2.shape[0] == 2 and
                    a.head == self.head and a.head in self._HEAD_CODES and
                    a.w1.shape == self.w1.shape and a.w1.shape[0] % 8 == 0 for a in nets)
 
-    def _heads(self, other, flat, n0, out):
-        """_head over rows [0, n0) with this actor and [n0, n) with `other`:
-        dropout + lin1 per weight set (hipBLASLt into one [n, 512] buffer),
-        then LeakyReLU -> lin2 -> head for every row in ONE dt_actor_head
-        launch (include/dtactor.h), written into out [n, 2] f32."""
-        import ctypes
-        from aido1_amd import _lib
+    def _head_x3_ok(self, x, other=None):
+        """The actors' heads on x fit one dt_actor_head_x3_drop launch pair."""
+        nets = [self] if other is None else [self, other]
+        return (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and
+                tuple(x.shape[1:]) == (FLAT,) and
+                all(hasattr(a, 'w1x') and a.head == self.head and a.head in self._HEAD_CODES and
+                    tuple(a.w2.shape) == (2, 512) for a in nets))
+
+    def _head_path(self, flat, other=None):
+        """What runs the head on flat's rows (with `other`: over both weight
+        sets at once), in order of preference: 'x3' / 'f16', a fused launch
+        pair (_head_fused); 'addmm', a library GEMM per set and dt_actor_head
+        (_head_addmm); None, no launch serves them."""
+        if not flat.is_cuda or flat.shape[0] == 0:
+            return None
+        # a fused launch has one dropout rate and one mode for all its rows
         o = other if other is not None else self
-        if (hasattr(self, 'w1f') and hasattr(o, 'w1f') and flat.dtype == torch.float16
-                and flat.is_contiguous() and tuple(flat.shape[1:]) == (FLAT,)
-                and o.p_drop == self.p_drop and o.mode == self.mode):
-            return self._heads_f16(o, flat, n0, out)
+        one = o.p_drop == self.p_drop and o.mode == self.mode
+        if one and self._head_x3_ok(flat, other):
+            return 'x3'
+        if flat.dtype == torch.float16 and self._head_fusable(other):
+            if (one and hasattr(self, 'w1f') and hasattr(o, 'w1f') and
+                    flat.is_contiguous() and tuple(flat.shape[1:]) == (FLAT,)):
+                return 'f16'
+            return 'addmm'
+        return None
+
+    def _heads(self, other, flat, n0, out=None):
+        """dropout (reference mode) -> lin1 -> LeakyReLU -> lin2 -> head on
+        the flattened activations: rows [0, n0) with this actor's weights,
+        [n0, n) with `other`'s (None: every row with this actor's).  Returns
+        [n, 2] f32 (into `out` if given).  Where no launch covers both actors
+        (_head_path; different dropout rates or modes among the reasons) each
+        actor's rows go through its own head with its own rate; one actor
+        alone falls back to the torch ops (_head)."""
+        n = flat.shape[0]
+        path = self._head_path(flat, other)
+        if path is None and other is None:
+            y = self._head(flat)
+            return y if out is None else out.copy_(y)
+        if out is None:
+            out = torch.empty(n, 2, dtype=torch.float32, device=flat.device)
+        if path is None:
+            out[:n0] = self._heads(None, flat[:n0], n0)
+            out[n0:] = other._heads(None, flat[n0:], n - n0)
+            return out
+        o, n0 = (self, n) if other is None else (other, n0)
+        if path == 'addmm':
+            self._head_addmm(o, flat, n0, out)
+        elif path == 'x3':
+            self._head_fused('dt_actor_head_x3_drop', 'w1x', o, flat, n0, out)
+        else:
+            self._head_fused('dt_actor_head_f16_drop', 'w1f', o, flat, n0, out)
+        return out
+
+    _heads_x3 = _heads     # its former x3 copy's name (tests/test_gpu_actor_x3.py)
+
+    def _head(self, x):
+        """The head as torch ops in `dtype` (any device)."""
+        if self.mode == 'reference' and self.p_drop > 0:
+            x = F.dropout(x, self.p_drop, training=True)
+        x = F.leaky_relu(F.linear(x, self.w1, self.b1))
+        x = F.linear(x, self.w2, self.b2).float()
+        return apply_head(x, self.head, self.max_action)
+
+    def _head_addmm(self, o, flat, n0, out):
+        """The fp16 head without lin1's fragments: dropout + lin1 per weight
+        set (hipBLASLt into one [n, k] buffer), then LeakyReLU -> lin2 ->
+        head for every row in ONE dt_actor_head launch (include/dtactor.h)."""
         n, k = flat.shape[0], self.w1.shape[0]
         h = torch.empty(n, k, dtype=torch.float16, device=flat.device)
         for a, sl in ((self, slice(0, n0)), (o, slice(n0, n))):
@@ -870,7 +877,6 @@ class FusedActor(nn.Module):
             ctypes.c_void_p(torch.cuda.current_stream(flat.device).cuda_stream))
         if rc != 0:
             raise _lib.DtError('dt_actor_head failed (%d)' % rc)
-        return out
 
     def _drop_seed(self, p):
         """A fresh key for the head's folded dropout (one a call), from a
@@ -882,119 +888,36 @@ class FusedActor(nn.Module):
         self._drop_key[1] += 1
         return (self._drop_key[0] + 0x9E3779B9 * self._drop_key[1]) & 0xFFFFFFFF
 
-    def _heads_f16(self, o, flat, n0, out):
-        """The fast mode's head (dropout -> lin1 -> LeakyReLU -> lin2 -> head)
-        for both weight sets in one dt_actor_head_f16_drop launch pair: lin1
-        on fp16 MFMA with f32 accumulation, the dropout folded into its
-        staging (include/dtactor.h)."""
-        import ctypes
-        from aido1_amd import _lib
-        p = self.p_drop if self.mode == 'reference' else 0.0
-        L = _lib.lib()
-        n = flat.shape[0]
+    def _head_work(self, n, dev):
+        """The fused heads' workspace (lin1's partial sums), grown as needed."""
+        need = int(_lib.lib().dt_actor_head_x3_work_floats(n))
         work = getattr(self, '_hwork', None)
-        if work is None or work.numel() < L.dt_actor_head_x3_work_floats(n) or \
-                work.device != flat.device:
-            work = self._hwork = torch.empty(int(L.dt_actor_head_x3_work_floats(n)),
-                                             device=flat.device)
-        rc = L.dt_actor_head_f16_drop(
-            n, n0, FLAT, flat.data_ptr(), float(p), self._drop_seed(p), self.w1f.data_ptr(),
-            self.b1.data_ptr(), self.w2.data_ptr(), self.b2.data_ptr(), o.w1f.data_ptr(),
-            o.b1.data_ptr(), o.w2.data_ptr(), o.b2.data_ptr(), self._HEAD_CODES[self.head], 0.01,
-            work.data_ptr(), out.data_ptr(),
+        if work is None or work.numel() < need or work.device != dev:
+            work = self._hwork = torch.empty(need, device=dev)
+        return work
+
+    def _head_fused(self, entry, w1, o, flat, n0, out):
+        """The whole head for both weight sets in ONE launch pair of `entry`
+        (include/dtactor.h): lin1 from the fragments `w1` at float32 accuracy
+        (dt_actor_head_x3_drop) or on fp16 MFMA with f32 accumulation
+        (dt_actor_head_f16_drop), the dropout folded into its staging under a
+        fresh counter-based key."""
+        p =self.p_drop if self.mode == 'reference' else 0.0
+        n = flat.shape[0]
+        rc = getattr(_lib.lib(), entry)(
+            n, n0, FLAT, flat.data_ptr(), float(p), self._drop_seed(p),
+            getattr(self, w1).data_ptr(), self.b1.data_ptr(), self.w2.data_ptr(),
+            self.b2.data_ptr(), getattr(o, w1).data_ptr(), o.b1.data_ptr(), o.w2.data_ptr(),
+            o.b2.data_ptr(), self._HEAD_CODES[self.head], 0.01,
+            self._head_work(n, flat.device).data_ptr(), out.data_ptr(),
             ctypes.c_void_p(torch.cuda.current_stream(flat.device).cuda_stream))
         if rc != 0:
-            raise _lib.DtError('dt_actor_head_f16_drop failed (%d)' % rc)
-        return out
+            raise _lib.DtError('%s failed (%d)' % (entry, rc))
 
-    def _head_x3_ok(self, x, other=None):
-        nets = [self] if other is None else [self, other]
-        return (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and
-                tuple(x.shape[1:]) == (FLAT,) and
-                all(hasattr(a, 'w1x') and a.head in self._HEAD_CODES and
-                    tuple(a.w2.shape) == (2, 512) for a in nets))
 
-    def _heads_x3(self, other, x, n0, out):
-        """dropout (reference mode) -> lin1 -> LeakyReLU -> lin2 -> head at
-        float32 accuracy in ONE dt_actor_head_x3_drop launch pair
-        (include/dtactor.h; the dropout folded into lin1's staging): rows
-        [0, n0) with this actor's weights, [n0, n) with `other`'s."""
-        import ctypes
-        from aido1_amd import _lib
-        o = other if other is not None else self
-        p = self.p_drop if self.mode == 'reference' else 0.0
-        if p > 0 and o.p_drop != self.p_drop:     # one rate a launch: torch's dropout
-            x = F.dropout(x, p, training=True)
-            p = 0.0
-        # the dropout folded into lin1's staging (dt_actor_head_x3_drop): a
-        # fresh counter-based key a call, drawn from torch's generator once
-        seed = self._drop_seed(p)
-        L = _lib.lib()
-        n = x.shape[0]
-        work = getattr(self, '_hwork', None)
-        if work is None or work.numel() < L.dt_actor_head_x3_work_floats(n) or \
-                work.device != x.device:
-            work = self._hwork = torch.empty(int(L.dt_actor_head_x3_work_floats(n)),
-                                             device=x.device)
-        rc = L.dt_actor_head_x3_drop(
-            n, n0, FLAT, x.data_ptr(), float(p), seed, self.w1x.data_ptr(), self.b1.data_ptr(),
-            self.w2.data_ptr(), self.b2.data_ptr(), o.w1x.data_ptr(), o.b1.data_ptr(),
-            o.w2.data_ptr(), o.b2.data_ptr(), self._HEAD_CODES[self.head], 0.01, work.data_ptr(),
-            out.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-        if rc != 0:
-            raise _lib.DtError('dt_actor_head_x3 failed (%d)' % rc)
-        return out
-
-    def _head(self, x):
-        """dropout (reference mode) -> lin1 -> LeakyReLU -> lin2 -> head."""
-        if self._head_x3_ok(x) and x.shape[0] > 0:
-            out = torch.empty(x.shape[0], 2, dtype=torch.float32, device=x.device)
-            return self._heads_x3(None, x, x.shape[0], out)
-        if self.mode == 'reference' and self.p_drop > 0:
-            x = F.dropout(x, self.p_drop, training=True)
-        x = F.leaky_relu(F.linear(x, self.w1, self.b1))
-        x = F.linear(x, self.w2, self.b2).float()
-        return apply_head(x, self.head, self.max_action)
-
-    @torch.no_grad()
-    def forward(self, x, order=None):
-        """x: [N,3,120,160] stack (oldest first), or the frame ring with
-        `order` = ring slots oldest->newest (RenderOutput.order()); grey
-        float32 or palette-index uint8 frames (render.py)."""
-        # MIOpen's heuristic choice for conv2 at these shapes is a 2.5 ms CK
-        # kernel; its benchmark-mode search finds a 0.57 ms one (once per shape)
-        with torch.backends.cudnn.flags(enabled=True, benchmark=True,
-                                        deterministic=False, allow_tf32=False):
-            return self._forward(x, order)
-
-    def _forward(self, x, order):
-        ref = self.mode == 'reference'
-        if self._x3_input(x):
-            # the reference-precision product path: the float32-accurate HIP convs
-            return self._head(self._convs_x3(x, order if order is not None else [0, 1, 2]))
-        if (x.is_cuda and self.dtype == torch.float16 and
-                x.dtype in (torch.float32, torch.uint8) and
-                x.is_contiguous() and tuple(x.shape[2:]) == (120, 160) and x.shape[1] >= 3 and
-                self.w[0].shape == (32, 3, 8, 8)):
-            # the fp16 product path: all four convs are the hand-written MFMA kernels
-            x = self._convs_hip(x, order if order is not None else [0, 1, 2])
-            if self._head_fusable() and x.shape[0] > 0:
-                out = torch.empty(x.shape[0], 2, dtype=torch.float32, device=x.device)
-                return self._heads(None, x, x.shape[0], out)
-        else:
-            from aido1_amd.render import as_gray
-            x = as_gray(x)
-            w0 = self.w[0]
-            if order is not None:
-                inv = sorted(range(len(order)), key=lambda c: order[c])
-                w0 = w0[:, inv].contiguous(memory_format=torch.channels_last)
-            x = x.to(self.dtype, memory_format=torch.channels_last)
-            for i in range(4):
-                x = F.conv2d(x, w0 if i == 0 else self.w[i], self.b[i], stride=self.strides[i])
-                x = self._lrelu_sample_norm(x, i) if ref else F.leaky_relu(x)
-            # flatten in NCHW order, as the reference's view(x.size(0), -1)
-            x = x.contiguous().flatten(1)
-        return self._head(x)
+def _take(src, idx):
+    """src's logical elements idx as a 1-D tensor, zero where idx is -1."""
+    return torch.take(src.detach(), idx.clamp(min=0)).masked_fill_(idx < 0, 0)
 
 
 def copy_grouped(dsts, srcs):

@@ -955,22 +955,8 @@ int conv1_launch(const void* ring, int32_t n, int32_t slots, const int32_t* orde
   if (set2 && (set2->n0 < 0 || set2->n0 > n || !set2->wfrag || !set2->bias)) return DT_E_ARG;
   if (n == 0) return DT_OK;
   static int grid = 0;   // resident workgroups, persistent
-  if (!grid) {
-    int dev = 0, cus = 256, per = 2;
-    if (hipGetDevice(&dev) == hipSuccess)
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, conv1s_kernel<true, kIdx>, kSThreads,
-                                                     0) != hipSuccess ||
-        per < 1)
-      per = 1;
-    if (DTCONV1_PER > 0 && DTCONV1_PER < per) per = DTCONV1_PER;
-    grid = per * cus;
-  }
-  WeightSplit ws{};
-  if (set2) {
-    ws.wfrag = set2->wfrag;
-    ws.bias = set2->bias;
-  }
+  if (!grid) grid = resident_grid(conv1s_kernel<true, kIdx>, kSThreads, DTCONV1_PER);
+  WeightSplit ws = weight_split(set2);
   const int g = split_grid(ws, n, set2 ? set2->n0 : n, grid);
   if (partials)
     hipLaunchKernelGGL((conv1s_kernel<true, kIdx>), dim3(g), dim3(kSThreads), 0,
@@ -1051,15 +1037,7 @@ extern "C" int dt_conv32_split(int32_t layer, int32_t n, const void* x, const vo
                ((out_beta != nullptr) != (set2->out_beta != nullptr))))
     return DT_E_ARG;
   if (n == 0) return DT_OK;
-  WeightSplit ws{};
-  if (set2) {
-    ws.wfrag = set2->wfrag;
-    ws.bias = set2->bias;
-    ws.in_gamma = set2->in_gamma;
-    ws.in_beta = set2->in_beta;
-    ws.out_gamma = set2->out_gamma;
-    ws.out_beta = set2->out_beta;
-  }
+  const WeightSplit ws = weight_split(set2);
   const int n0 = set2 ? set2->n0 : n;
   hipStream_t s = (hipStream_t)stream;
   switch (layer) {

@@ -10,6 +10,8 @@
 
 #include <cstdint>
 
+#include "../../include/dtactor.h"
+
 namespace dtconv {
 
 using half8 = __attribute__((ext_vector_type(8))) _Float16;
@@ -82,6 +84,20 @@ inline int split_grid(WeightSplit& ws, int n, int n0, int grid) {
   ws.g0 = n0 < g0 ? n0 : g0;
   const int g1 = (n - n0) < g1raw ? (n - n0) : g1raw;
   return ws.g0 + g1;
+}
+// host: the second set of a launch from the C ABI's dt_conv_set (NULL: one set,
+// all zero); n0 / g0 are split_grid's
+inline WeightSplit weight_split(const dt_conv_set* set2) {
+  WeightSplit ws{};
+  if (set2) {
+    ws.wfrag = set2->wfrag;
+    ws.bias = set2->bias;
+    ws.in_gamma = set2->in_gamma;
+    ws.in_beta = set2->in_beta;
+    ws.out_gamma = set2->out_gamma;
+    ws.out_beta = set2->out_beta;
+  }
+  return ws;
 }
 
 // ---- conv1's row stream ------------------------------------------------------------

@@ -1000,11 +1000,7 @@ int conv1x_launch(const void* ring, int32_t n, int32_t slots, const int32_t* ord
   if (n == 0) return DT_OK;
   static int grid = 0;
   if (!grid) grid = resident_grid(conv1x_kernel<kIdx>, kSThreads, 0);
-  WeightSplit ws{};
-  if (set2) {
-    ws.wfrag = set2->wfrag;
-    ws.bias = set2->bias;
-  }
+  WeightSplit ws = weight_split(set2);
   const int g = split_grid(ws, n, set2 ? set2->n0 : n, grid);
   hipLaunchKernelGGL((conv1x_kernel<kIdx>), dim3(g), dim3(kSThreads), 0, (hipStream_t)stream, n,
                      ring, slots, order[0], order[1], order[2], (const half8*)wfrag, bias,
@@ -1095,15 +1091,7 @@ extern "C" int dt_conv32x_split(int32_t layer, int32_t n, const void* x, const f
                !set2->in_beta || (last && (!set2->out_gamma || !set2->out_beta))))
     return DT_E_ARG;
   if (n == 0) return DT_OK;
-  WeightSplit ws{};
-  if (set2) {
-    ws.wfrag = set2->wfrag;
-    ws.bias = set2->bias;
-    ws.in_gamma = set2->in_gamma;
-    ws.in_beta = set2->in_beta;
-    ws.out_gamma = set2->out_gamma;
-    ws.out_beta = set2->out_beta;
-  }
+  const WeightSplit ws = weight_split(set2);
   const int n0 = set2 ? set2->n0 : n;
   hipStream_t s = (hipStream_t)stream;
   switch (layer) {

@@ -103,29 +103,56 @@ def test_fused_reference_mode_dropout_live_and_refresh():
     assert torch.equal(f.w[2], b.layers()[0][2].weight.contiguous(memory_format=torch.channels_last))
 
 
-@pytest.mark.parametrize('mode', ['reference', 'eval'])
-def test_refresh_fragments_match_fragment_builders(mode):
+def _head_fragments(w1):
+    """lin1's weights [512, 4032] in the fused heads' fragment layout
+    [16, 252, 64, 8] (include/dtactor.h), written out: element [t][s][l][j] =
+    w1[32 t + l % 32][16 s + 8 (l // 32) + j]."""
+    t = torch.arange(16).view(16, 1, 1, 1)
+    s = torch.arange(252).view(1, 252, 1, 1)
+    ln = torch.arange(64).view(1, 1, 64, 1)
+    j = torch.arange(8).view(1, 1, 1, 8)
+    return w1[32 * t + ln % 32, 16 * s + 8 * (ln // 32) + j]
+
+
+@pytest.mark.parametrize('mode,dtype', [('reference', torch.float16), ('eval', torch.float16),
+                                        ('reference', torch.float32)],
+                         ids=['reference', 'eval', 'reference-float32'])
+def test_refresh_fragments_match_fragment_builders(mode, dtype):
     """refresh() gathers the MFMA fragments through index maps; they equal
     conv1_fragments / conv32_fragments of the weights it derives, and the f32
-    biases are the layers' (folded) biases."""
+    biases are the layers' (folded) biases.  The heads' lin1 fragments equal
+    the layout written out in _head_fragments, and the float32-accurate
+    chain's are the float32 fragments (conv1's and lin1's as (hi, lo) fp16
+    halves): the eager refresh and dt_refresh_copy's table share one
+    description, so their agreement alone does not pin the layouts."""
     from aido1_amd.actor import (ConfigActor, FusedActor, conv1_fragments,
-                                 conv32_fragments)
+                                 conv32_fragments, split_hl)
     torch.manual_seed(3)
     a = ConfigActor(golden('reference_config.json')['model']['actor'])
     for m in a.modules():
         if isinstance(m, torch.nn.BatchNorm2d):
             m.running_mean.uniform_(-0.5, 0.5)
             m.running_var.uniform_(0.5, 2.0)
-    f = FusedActor(a, dtype=torch.float16, mode=mode)
+    f = FusedActor(a, dtype=dtype, mode=mode)
+    # the fp16 chain's fragments: fp16 of the acting weights (exact for float32 ones too)
     assert torch.equal(f.w0frag, conv1_fragments(f.w[0].float()))
     for i in range(1, 4):
         assert torch.equal(f.wfrag[i - 1], conv32_fragments(f.w[i].float()))
-    convs = a.layers()[0]
+    convs, _, lin1, _ = a.layers()
     if mode == 'reference':
         for i in range(4):
             assert torch.equal(f.bf[i], convs[i].bias.detach())
     else:
         assert torch.allclose(f.bf, torch.stack([b.float() for b in f.b]), rtol=1e-3, atol=1e-3)
+    if dtype == torch.float16:   # from the acting lin1 weights: folded in eval mode
+        w1 = lin1.weight.detach() if mode == 'reference' else f.w1
+        assert torch.equal(f.w1f, _head_fragments(w1).half())
+    else:
+        ws = [c.weight.detach() for c in convs]
+        assert torch.equal(f.w0x, split_hl(conv1_fragments(ws[0], torch.float32)))
+        for i in range(1, 4):
+            assert torch.equal(f.wx32[i - 1], conv32_fragments(ws[i], torch.float32))
+        assert torch.equal(f.w1x, split_hl(_head_fragments(lin1.weight.detach())))
 
 
 def test_bench_actor_f64_is_batch_of_one_train_mode():

@@ -246,6 +246,28 @@ def test_head_x3_matches_float64(gpu, n, n0):
     assert (out.double() - want).abs().max().item() < 2e-6
 
 
+def test_pair_head_unequal_dropout_uses_each_rate(gpu):
+    """Two actors with different dropout rates share no fused head launch
+    (one launch has one rate): each actor's rows go through its own head
+    with its own rate.  At p = 0 the second actor's rows are deterministic
+    and equal its own head's bit for bit; the first actor's rows draw a
+    fresh mask a call.  n0 = 33 puts the split inside a 32-row tile."""
+    from aido1_amd.actor import FLAT, ConfigActor, FusedActor
+    cfg = golden('reference_config.json')['model']['actor']
+    torch.manual_seed(5)
+    fa = FusedActor(ConfigActor(cfg).to(gpu), dtype=torch.float32, mode='reference')
+    fb = FusedActor(ConfigActor(cfg).to(gpu), dtype=torch.float32, mode='reference')
+    fa.p_drop, fb.p_drop = 0.5, 0.0
+    n, n0 = 64, 33
+    flat = torch.randn(n, FLAT, device=gpu) * 0.5
+    outs = [fa._heads(fb, flat, n0).clone() for _ in range(2)]
+    own = fb._heads(None, flat[n0:], n - n0)
+    for out in outs:
+        assert torch.isfinite(out).all()
+        assert torch.equal(out[n0:], own)
+    assert not torch.equal(outs[0][:n0], outs[1][:n0])
+
+
 def _drop_hash(x):
     x = x.astype(np.uint64) & 0xFFFFFFFF
     x ^= x >> 16

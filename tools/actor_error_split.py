@@ -45,13 +45,12 @@ with torch.no_grad():
         with torch.backends.cudnn.flags(enabled=True, benchmark=True, deterministic=False,
                                         allow_tf32=False):
             flat32 = f32_flat(a32, stack)
-        flat16 = a16._convs_hip(ring, order)
+        flat16 = a16._convs(ring, order)
         full16 = a16(ring, order)
-        full32 = a32._head(flat32)
-        trunk = a32._head(flat16.float())          # f32 head on the fp16 trunk
+        full32 = a32._heads(None, flat32, flat32.shape[0])
+        trunk = a32._heads(None, flat16.float(), flat16.shape[0])          # f32 head on the fp16 trunk
         # the head in fp16 on the f32 trunk
-        head16 = a16._heads(None, flat32.half(), flat32.shape[0],
-                            torch.empty(flat32.shape[0], 2, device=dev))
+        head16 = a16._heads(None, flat32.half(), flat32.shape[0])
         h32 = F.linear(flat32, a32.w1, a32.b1)
         h16 = F.linear(flat16, a16.w1, a16.b1).float()
         df = (flat16.float() - flat32).abs()

@@ -50,7 +50,7 @@ def main():
             import ctypes
             from aido1_amd import _lib
             L = _lib.lib()
-            B = fa._x3_buffers(n, dev)
+            B = fa._chain_buffers(n, dev)
             st = torch.cuda.current_stream().cuda_stream
             o = (ctypes.c_int32 * 3)(*order)
             calls = {
