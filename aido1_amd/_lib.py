@@ -22,7 +22,7 @@ SOURCES = ['dtsim.hip', 'dtrender.hip', 'dtreplay.hip', 'dtactor.hip', 'dtconv.h
 HEADERS = ['dtsim_common.h', 'dtrender.h', 'dtsync.h', 'dtconv_common.h']
 PUBLIC_HEADERS = ['dtsim.h', 'dtreplay.h', 'dtactor.h', 'dttrain.h', 'dtupd.h', 'dthead.h']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 HIP_FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-shared', '-std=c++17',
              '-ffp-contract=off', '-munsafe-fp-atomics']
@@ -224,6 +224,9 @@ def bind(L):
         'dt_bn_leaky_bwd': (ctypes.c_int, [i64, vp, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp,
                                            vp, vp, vp, vp]),
         'dt_adam': (ctypes.c_int, [i32, vp, vp, vp, vp, f64, f64, f64, vp, vp, i32, i32, vp]),
+        'dt_adamw': (ctypes.c_int, [i32, vp, vp, vp, vp, f64, f64, f64, f64, vp, vp, i32, i32,
+                                    vp]),
+        'dt_sgd': (ctypes.c_int, [i32, vp, vp, vp, f64, f64, vp, i32, i32, vp]),
         'dt_guard_scan': (ctypes.c_int, [i32, vp, vp, vp]),
         # dtupd.h
         'dt_upd_conv_fwd': (ctypes.c_int, [i32, i32, i32, i32, i32, i32, vp, vp, vp, vp]),

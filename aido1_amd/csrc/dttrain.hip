@@ -417,6 +417,73 @@ adam_kernel(const dt_mt_tensor* __restrict__ tensors, const int32_t* __restrict_
   }
 }
 
+// models/adamw.py:86-108: the bias corrections sit in step_size, eps joins the
+// uncorrected root, then the decoupled decay on the stepped parameter
+__global__ void __launch_bounds__(kMtThreads)
+adamw_kernel(const dt_mt_tensor* __restrict__ tensors, const int32_t* __restrict__ chunks,
+             double* __restrict__ step, const double* __restrict__ lr, double beta1, double beta2,
+             double eps, double weight_decay, unsigned int* __restrict__ counter,
+             int32_t* __restrict__ guard, int grad_bit, int param_bit) {
+  const dt_mt_tensor t = tensors[chunks[2 * blockIdx.x]];
+  const int64_t start = (int64_t)chunks[2 * blockIdx.x + 1] * DT_MT_CHUNK;
+  const int64_t end = start + DT_MT_CHUNK < t.n ? start + DT_MT_CHUNK : t.n;
+  const double st = *step + 1.0;
+  const double l = *lr;
+  // Python doubles passed to float32 element ops
+  const float step_size = (float)(l * sqrt(1.0 - pow(beta2, st)) / (1.0 - pow(beta1, st)));
+  const float decay = (float)(l * weight_decay);
+  const float b1 = (float)beta1, ob1 = (float)(1.0 - beta1);
+  const float b2 = (float)beta2, ob2 = (float)(1.0 - beta2);
+  const float fe = (float)eps;
+  bool bad_g = false, bad_p = false;
+  for (int64_t i = start + threadIdx.x; i < end; i += kMtThreads) {
+    const float g = t.b[i];
+    bad_g = bad_g || !finitef(g);
+    float m = t.c[i] * b1;                                              // mul_
+    m = m + ob1 * g;                                                    // add_(alpha)
+    float v = t.d[i] * b2;                                              // mul_
+    v = v + ob2 * g * g;                                                // addcmul_
+    const float den = sqrtf(v) + fe;                                    // sqrt, add_
+    float p = t.a[i] - step_size * (m / den);                           // addcdiv_
+    p = p - p * decay;                                                  // sub_(p * (lr * wd))
+    bad_p = bad_p || !finitef(p);
+    t.a[i] = p;
+    t.c[i] = m;
+    t.d[i] = v;
+  }
+  guard_raise(guard, grad_bit, bad_g);
+  guard_raise(guard, param_bit, bad_p);
+  // the step count moves once every workgroup has read it
+  if (last_arrival(counter) && threadIdx.x == 0)
+    __hip_atomic_store(step, st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// torch.optim.SGD with momentum and weight decay (dampening 0, no Nesterov)
+__global__ void __launch_bounds__(kMtThreads)
+sgd_kernel(const dt_mt_tensor* __restrict__ tensors, const int32_t* __restrict__ chunks,
+           const double* __restrict__ lr, float momentum, float weight_decay,
+           int32_t* __restrict__ guard, int grad_bit, int param_bit) {
+  const dt_mt_tensor t = tensors[chunks[2 * blockIdx.x]];
+  const int64_t start = (int64_t)chunks[2 * blockIdx.x + 1] * DT_MT_CHUNK;
+  const int64_t end = start + DT_MT_CHUNK < t.n ? start + DT_MT_CHUNK : t.n;
+  const float l = (float)*lr;
+  bool bad_g = false, bad_p = false;
+  for (int64_t i = start + threadIdx.x; i < end; i += kMtThreads) {
+    const float g = t.b[i];
+    bad_g = bad_g || !finitef(g);
+    float p = t.a[i];
+    const float gd = g + weight_decay * p;                              // add(alpha = wd)
+    float c = t.c[i] * momentum;                                        // mul_
+    c = c + gd;                                                         // add_
+    p = p - l * c;                                                      // add_(alpha = -lr)
+    bad_p = bad_p || !finitef(p);
+    t.a[i] = p;
+    t.c[i] = c;
+  }
+  guard_raise(guard, grad_bit, bad_g);
+  guard_raise(guard, param_bit, bad_p);
+}
+
 __global__ void __launch_bounds__(kMtThreads)
 soft_update_kernel(const dt_mt_tensor* __restrict__ tensors, const int32_t* __restrict__ chunks,
                    float keep, float tau) {
@@ -532,6 +599,31 @@ int dt_adam(int32_t n_chunks, const dt_mt_tensor* tensors, const int32_t* chunks
   hipLaunchKernelGGL(adam_kernel, dim3(n_chunks), dim3(kMtThreads), 0, (hipStream_t)stream,
                      tensors, chunks, step, lr, beta1, beta2, eps, counter, guard, (int)grad_bit,
                      (int)param_bit);
+  return hipGetLastError() == hipSuccess ? DT_OK : DT_E_HIP;
+}
+
+int dt_adamw(int32_t n_chunks, const dt_mt_tensor* tensors, const int32_t* chunks, double* step,
+             const double* lr, double beta1, double beta2, double eps, double weight_decay,
+             uint32_t* counter, int32_t* guard, int32_t grad_bit, int32_t param_bit,
+             void* stream) {
+  if (n_chunks < 0 || (n_chunks > 0 && (!tensors || !chunks || !step || !lr || !counter)))
+    return DT_E_ARG;
+  if (n_chunks == 0) return DT_OK;
+  hipLaunchKernelGGL(adamw_kernel, dim3(n_chunks), dim3(kMtThreads), 0, (hipStream_t)stream,
+                     tensors, chunks, step, lr, beta1, beta2, eps, weight_decay, counter, guard,
+                     (int)grad_bit, (int)param_bit);
+  return hipGetLastError() == hipSuccess ? DT_OK : DT_E_HIP;
+}
+
+int dt_sgd(int32_t n_chunks, const dt_mt_tensor* tensors, const int32_t* chunks, const double* lr,
+           double momentum, double weight_decay, int32_t* guard, int32_t grad_bit,
+           int32_t param_bit, void* stream) {
+  if (n_chunks < 0 || (n_chunks > 0 && (!tensors || !chunks || !lr))) return DT_E_ARG;
+  if (n_chunks == 0) return DT_OK;
+  // torch: the Python doubles as float32 scalars of the element ops
+  hipLaunchKernelGGL(sgd_kernel, dim3(n_chunks), dim3(kMtThreads), 0, (hipStream_t)stream,
+                     tensors, chunks, lr, (float)momentum, (float)weight_decay, guard,
+                     (int)grad_bit, (int)param_bit);
   return hipGetLastError() == hipSuccess ? DT_OK : DT_E_HIP;
 }
 

@@ -12,8 +12,8 @@ stage, the tick at which it first fired); nothing is read back until
 order, earliest first -- so the first named stage is where a NaN entered.
 
 On the GPU the reports come from the kernels themselves (dt_bn_leaky_fwd /
-_bwd, dt_adam) and from dt_guard_scan launches over the stage outputs, all
-graph-capturable; on the CPU (the float64 parity path of the tests) the same
+_bwd, dt_adam / dt_adamw / dt_sgd) and from dt_guard_scan launches over the
+stage outputs, all graph-capturable; on the CPU (the float64 parity path of the tests) the same
 bits are set with torch ops.
 """
 import ctypes

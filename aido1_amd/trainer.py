@@ -47,7 +47,7 @@ import torch.nn.functional as F
 from aido1_amd.distributed import GradAllReduce, world
 from aido1_amd.explore import create_decay_fn
 from aido1_amd.guard import Guard
-from aido1_amd.optim import DeviceAdam, SoftUpdate, make_optimizer
+from aido1_amd.optim import DeviceStep, SoftUpdate, make_optimizer
 from aido1_amd import train_ops
 
 
@@ -113,12 +113,14 @@ class DDPGTrainer:
             m.to(memory_format=torch.channels_last)
             m.train()                           # managers.py:264-268 _prime_model
         self.graph = bool(graph) and self.device.type == 'cuda'
-        if self.graph and t['optimizer'] != 'adam':
-            raise NotImplementedError('graph capture needs the capturable Adam')
+        # an unknown kind raises NotImplementedError in make_optimizer
         self.actor_optim = make_optimizer(t['optimizer'], self.actor.parameters(), self.graph,
                                           self.device)
         self.critic_optim = make_optimizer(t['optimizer'], self.critic.parameters(), self.graph,
                                            self.device)
+        if self.graph and not all(isinstance(opt, DeviceStep)
+                                  for opt in (self.actor_optim, self.critic_optim)):
+            raise NotImplementedError('graph capture needs an optimiser with a device step')
         # non-finite guards (guard.py): every stage reports into one device
         # block, read only by check()
         self.guard = guard if guard is not None else Guard(self.device)
@@ -127,7 +129,7 @@ class DDPGTrainer:
                 train_ops.attach_guard(m, self.guard)
         for opt, stages in ((self.actor_optim, ('actor_grad', 'actor_param')),
                             (self.critic_optim, ('critic_grad', 'critic_param'))):
-            if isinstance(opt, DeviceAdam):
+            if isinstance(opt, DeviceStep):
                 opt.set_guard(self.guard, *stages)
         self.warmup = warmup
         # stream layout of the stages (A/B: tools/update_only.py AB_ATTR=...)
@@ -198,10 +200,10 @@ class DDPGTrainer:
         grads = torch.autograd.grad(loss, params, grad_outputs=one, allow_unused=True,
                                     materialize_grads=True)
         opt = self.actor_optim if module is self.actor else self.critic_optim
-        if (self.graph and isinstance(opt, DeviceAdam) and len(params) == len(list(
+        if (self.graph and isinstance(opt, DeviceStep) and len(params) == len(list(
                 module.parameters())) and (self.sync_actor if module is self.actor
                                             else self.sync_critic) is None):
-            # graph mode, one rank: dt_adam reads the autograd outputs
+            # graph mode, one rank: the device step reads the autograd outputs
             # themselves (their addresses are fixed in the graph's pool), so
             # no copy into .grad (two multi-tensor kernels an update)
             self._pending_grads[id(module)] = list(grads)
@@ -244,9 +246,10 @@ class DDPGTrainer:
                 t.record_stream(cur)
 
     def _opt_step(self, opt, module, grad_stage, param_stage):
-        """opt.step() with its gradients and results guarded: DeviceAdam reports
-        from inside dt_adam, any other optimiser is scanned around."""
-        if isinstance(opt, DeviceAdam):
+        """opt.step() with its gradients and results guarded: a device optimiser
+        (optim.DeviceStep) reports from inside its kernel, any other is scanned
+        around."""
+        if isinstance(opt, DeviceStep):
             opt.step(grads=self._pending_grads.pop(id(module), None))
             return
         params = [p for p in module.parameters() if p.grad is not None]
@@ -421,7 +424,7 @@ class DDPGTrainer:
                     st()
             self._graphs.append(g)
         for opt in (self.actor_optim, self.critic_optim):
-            if isinstance(opt, DeviceAdam):
+            if isinstance(opt, DeviceStep):
                 opt.finish_capture()
 
     def update(self, train_data):

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define DT_ABI_VERSION 13 /* 2: curves per tile vary (curve_start), intersections;
+#define DT_ABI_VERSION 14 /* 2: curves per tile vary (curve_start), intersections;
                              3: static objects in dt_map, safety_rad_mult;
                              4: dt_render_io.pose / list_cap, dt_copy_pose,
                                 dt_step_many pose output;
@@ -56,7 +56,9 @@ extern "C" {
                             12: dtupd.h dt_upd_linear_fwd_drop / _dgrad_drop
                                 (dropout folded into the linears);
                             13: dtactor.h dt_actor_head_x3_drop,
-                                dt_actor_head_f16_drop */
+                                dt_actor_head_f16_drop;
+                            14: dttrain.h dt_adamw, dt_sgd (the reference's
+                                other two optimisers as device steps) */
 
 /* error codes */
 #define DT_OK 0

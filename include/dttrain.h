@@ -121,6 +121,41 @@ int dt_adam(int32_t n_chunks, const dt_mt_tensor* tensors, const int32_t* chunks
             const double* lr, double beta1, double beta2, double eps, uint32_t* counter,
             int32_t* guard, int32_t grad_bit, int32_t param_bit, void* stream);
 
+/* The reference's AdamW step (models/adamw.py:86-108; trainers.py:258-268
+ * "adamw"), a = param, b = grad, c = exp_avg, d = exp_avg_sq.  Not torch
+ * Adam's expression: the bias corrections sit in step_size and eps joins the
+ * uncorrected root.  Per element, every op rounded to float32 in this order:
+ *   t = *step + 1 (*step is written back by the last workgroup);
+ *   c = c * beta1;  c = c + (1 - beta1) * b;
+ *   d = d * beta2;  d = d + ((1 - beta2) * b) * b;
+ *   den = sqrt(d) + eps;
+ *   a = a - step_size * (c / den);
+ *   a = a - a * decay
+ * with step_size = lr * sqrt(1 - beta2^t) / (1 - beta1^t) and
+ * decay = lr * weight_decay computed in float64 from *step and *lr (device
+ * float64) and rounded once to float32; beta1, 1 - beta1, beta2, 1 - beta2
+ * and eps are rounded to float32 once each.  No product is fused into the add
+ * after it, so a zero gradient on zero moments leaves a - a * decay exactly.
+ * counter and guard as dt_adam's. */
+int dt_adamw(int32_t n_chunks, const dt_mt_tensor* tensors, const int32_t* chunks, double* step,
+             const double* lr, double beta1, double beta2, double eps, double weight_decay,
+             uint32_t* counter, int32_t* guard, int32_t grad_bit, int32_t param_bit,
+             void* stream);
+
+/* torch.optim.SGD's step with momentum and weight decay, dampening 0, no
+ * Nesterov (trainers.py:258-268 "sgd"), a = param, b = grad,
+ * c = momentum_buffer.  Per element, every op rounded to float32 in this order:
+ *   g = b + weight_decay * a;
+ *   c = c * momentum;  c = c + g;
+ *   a = a - lr * c
+ * with *lr (device float64), momentum and weight_decay rounded to float32 once
+ * each.  The buffer starts at zero: 0 * momentum + g is g, which is torch's
+ * first step (buf = clone(g)), so there is no step counter and no first-step
+ * branch.  guard as dt_adam's (grad_bit looks at b, not at g). */
+int dt_sgd(int32_t n_chunks, const dt_mt_tensor* tensors, const int32_t* chunks, const double* lr,
+           double momentum, double weight_decay, int32_t* guard, int32_t grad_bit,
+           int32_t param_bit, void* stream);
+
 /* Soft target update (models/torch_utils.py:5-9), a = target, b = source:
  * a = a * (1 - tau) + b * tau, the two products rounded separately. */
 int dt_soft_update(int32_t n_chunks, const dt_mt_tensor* tensors, const int32_t* chunks,

@@ -1,7 +1,7 @@
 """Diagnostic (GPU): the DDPG update alone (config.json networks with their
 dropout, batch 64, graph mode) on one synthetic batch, for a per-update kernel
 profile: rocprofv3 --kernel-trace --stats -- python3 tools/update_only.py
-Prints the median update time over the timed updates."""
+OPTIMIZER=adam|adamw|sgd overrides the config's training.optimizer.  Prints the median update time over the timed updates."""
 import json
 import os
 import sys
@@ -20,6 +20,8 @@ def main():
     with open(os.path.join(os.path.dirname(__file__), '..', 'aido1_amd', 'configs',
                            'reference_config.json')) as f:
         cfg = json.load(f)
+    if os.environ.get('OPTIMIZER'):      # adam | adamw | sgd (trainers.py:258-268)
+        cfg['training']['optimizer'] = os.environ['OPTIMIZER']
     torch.manual_seed(0)
     dev = torch.device('cuda', 0)
     tr = DDPGTrainer(cfg, ConfigActor(cfg['model']['actor']), ConfigCritic(cfg['model']['critic']),
