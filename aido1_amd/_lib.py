@@ -216,6 +216,8 @@ def bind(L):
         'dt_frame_add': (ctypes.c_int, [i32, i64, vp, i64, vp, i32, vp, vp, i32, vp, vp, vp]),
         'dt_frame_gather': (ctypes.c_int, [i32, vp, vp, i32, i64, i32, vp, vp, vp, vp, vp,
                                            vp, vp, vp, vp, vp, vp]),
+        'dt_frame_gather_w': (ctypes.c_int, [i32, vp, vp, i32, i64, i32, vp, vp, vp, vp, vp,
+                                             vp, vp, vp, vp, vp, vp, vp, vp]),
         # dttrain.h
         'dt_train_work_floats': (i64, [i64]),
         'dt_bn_leaky_fwd': (ctypes.c_int, [i64, vp, vp, ctypes.c_float, vp, vp, ctypes.c_float,
@@ -268,6 +270,8 @@ def bind(L):
                                          ctypes.c_float, vp, vp]),
         'dt_loss': (ctypes.c_int, [i32, i32, vp, vp, vp, vp]),
         'dt_loss_bwd': (ctypes.c_int, [i32, i32, vp, vp, vp, vp, vp]),
+        'dt_loss_w': (ctypes.c_int, [i32, i32, vp, vp, vp, vp, vp]),
+        'dt_loss_w_bwd': (ctypes.c_int, [i32, i32, vp, vp, vp, vp, vp, vp]),
         # dtactor.h
         'dt_sample_norm': (ctypes.c_int, [vp, vp, i32, i32, i32, vp, vp, ctypes.c_float,
                                           ctypes.c_float, i32, vp]),

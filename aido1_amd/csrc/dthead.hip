@@ -367,6 +367,45 @@ __global__ void __launch_bounds__(kLossThreads) loss_bwd_kernel(int kind, int m,
     da[i] = kind == 0 ? norm * (a[i] - b[i]) * gv : -(gv / (float)m);
 }
 
+// The critic loss under prioritized replay's importance weights (dt_loss_w):
+// kind 0: mean(w (a - b)^2); kind 2: mean(w l(a - b)), l torch's smooth-L1 at
+// beta = 1.  loss_kernel's form: f32 terms, widened, the same f64 sum order.
+// w multiplies last (and not at all for NULL), so ones give kind 0 of
+// loss_kernel bit for bit.
+__device__ __forceinline__ float smooth_l1(float d) {
+  const float z = fabsf(d);
+  return z < 1.0f ? 0.5f * d * d : z - 0.5f;
+}
+
+__global__ void __launch_bounds__(kLossThreads) loss_w_kernel(int kind, int m, const float* a,
+                                                              const float* b, const float* w,
+                                                              float* loss) {
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < m; i += kLossThreads) {
+    const float d = a[i] - b[i];
+    float t = kind == 0 ? d * d : smooth_l1(d);
+    if (w) t = t * w[i];
+    acc += (double)t;
+  }
+  const double t = block_sum(acc);
+  if (threadIdx.x == 0) *loss = (float)(t / m);
+}
+
+// kind 0: (2 / m) (a - b) g w (loss_bwd_kernel's product, then w); kind 2:
+// (1 / m) l'(a - b) g w, l'(d) = d inside (-1, 1), sign(d) outside
+__global__ void __launch_bounds__(kLossThreads) loss_w_bwd_kernel(int kind, int m, const float* a,
+                                                                  const float* b, const float* w,
+                                                                  const float* g, float* da) {
+  const float gv = *g;
+  const float norm = (kind == 0 ? 2.0f : 1.0f) / (float)m;
+  for (int i = blockIdx.x * kLossThreads + threadIdx.x; i < m; i += gridDim.x * kLossThreads) {
+    const float d = a[i] - b[i];
+    const float dl = (kind == 0 || fabsf(d) < 1.0f) ? d : (d > 0.0f ? 1.0f : -1.0f);
+    const float t = norm * dl * gv;
+    da[i] = w ? t * w[i] : t;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -397,6 +436,23 @@ int dt_loss_bwd(int32_t kind, int32_t m, const float* a, const float* b, const f
   const int grid = (m + kLossThreads - 1) / kLossThreads;
   hipLaunchKernelGGL(loss_bwd_kernel, dim3(grid < 64 ? grid : 64), dim3(kLossThreads), 0,
                      (hipStream_t)stream, kind, m, a, b, g, da);
+  return hipGetLastError() == hipSuccess ? DT_OK : DT_E_HIP;
+}
+
+int dt_loss_w(int32_t kind, int32_t m, const float* a, const float* b, const float* w,
+              float* loss, void* stream) {
+  if ((kind != 0 && kind != 2) || m < 1 || !a || !b || !loss) return DT_E_ARG;
+  hipLaunchKernelGGL(loss_w_kernel, dim3(1), dim3(kLossThreads), 0, (hipStream_t)stream, kind, m,
+                     a, b, w, loss);
+  return hipGetLastError() == hipSuccess ? DT_OK : DT_E_HIP;
+}
+
+int dt_loss_w_bwd(int32_t kind, int32_t m, const float* a, const float* b, const float* w,
+                  const float* g, float* da, void* stream) {
+  if ((kind != 0 && kind != 2) || m < 1 || !a || !b || !g || !da) return DT_E_ARG;
+  const int grid = (m + kLossThreads - 1) / kLossThreads;
+  hipLaunchKernelGGL(loss_w_bwd_kernel, dim3(grid < 64 ? grid : 64), dim3(kLossThreads), 0,
+                     (hipStream_t)stream, kind, m, a, b, w, g, da);
   return hipGetLastError() == hipSuccess ? DT_OK : DT_E_HIP;
 }
 

@@ -405,7 +405,9 @@ constexpr int kFrameThreads = 256;
 
 // dt_frame_gather: block (x, b) covers pixels [x * threads, ...) of sample b;
 // a thread reads its pixel from the k frames of obs and of next_obs (each
-// plane read coalesced) and writes the k-float NHWC pixel of each
+// plane read coalesced) and writes the k-float NHWC pixel of each; lanes 0-4
+// of block x == 0 write the sample's act / rew / notdone and (dt_frame_gather_w)
+// its importance weight, which is indexed by batch position, not by slot
 template <typename F>
 __device__ __forceinline__ float frame_px(const F* frames, int64_t i) {
   if constexpr (sizeof(F) == 1)
@@ -421,13 +423,15 @@ frame_gather_kernel(const int64_t* __restrict__ idx, const F* __restrict__ frame
                     const int32_t* __restrict__ next_ptr, const float* __restrict__ action,
                     const double* __restrict__ reward, const uint8_t* __restrict__ done,
                     float* __restrict__ obs, float* __restrict__ nxt, float* __restrict__ act,
-                    float* __restrict__ rew, float* __restrict__ notdone) {
+                    float* __restrict__ rew, float* __restrict__ notdone,
+                    const double* __restrict__ weights, float* __restrict__ w) {
   const int b = blockIdx.y;
   const int64_t i = idx[b];
   const int64_t px = (int64_t)blockIdx.x * kFrameThreads + threadIdx.x;
   if (blockIdx.x == 0 && threadIdx.x < 2) act[2 * b + threadIdx.x] = action[2 * i + threadIdx.x];
   if (blockIdx.x == 0 && threadIdx.x == 2) rew[b] = (float)reward[i];
   if (blockIdx.x == 0 && threadIdx.x == 3) notdone[b] = done[i] ? 0.0f : 1.0f;
+  if (blockIdx.x == 0 && threadIdx.x == 4 && w) w[b] = (float)weights[b];
   if (px >= hw) return;
   float* o = obs + ((int64_t)b * hw + px) * k;
   float* q = nxt + ((int64_t)b * hw + px) * k;
@@ -622,6 +626,16 @@ int dt_frame_gather(int32_t batch, const int64_t* idx, const void* frames, int32
                     int64_t hw, int32_t k, const int32_t* obs_ptr, const int32_t* next_ptr,
                     const float* action, const double* reward, const uint8_t* done, float* obs,
                     float* nxt, float* act, float* rew, float* notdone, void* stream) {
+  return dt_frame_gather_w(batch, idx, frames, frame_kind, hw, k, obs_ptr, next_ptr, action,
+                           reward, done, obs, nxt, act, rew, notdone, nullptr, nullptr, stream);
+}
+
+int dt_frame_gather_w(int32_t batch, const int64_t* idx, const void* frames, int32_t frame_kind,
+                      int64_t hw, int32_t k, const int32_t* obs_ptr, const int32_t* next_ptr,
+                      const float* action, const double* reward, const uint8_t* done, float* obs,
+                      float* nxt, float* act, float* rew, float* notdone, const double* weights,
+                      float* w, void* stream) {
+  if (!weights != !w) return DT_E_ARG;
   if (batch < 0 || hw < 1 || k < 1 || k > 4 || frame_kind < 0 || frame_kind > 1) return DT_E_ARG;
   if (batch == 0) return DT_OK;
   if (!idx || !frames || !obs_ptr || !next_ptr || !action || !reward || !done || !obs || !nxt ||
@@ -633,11 +647,11 @@ int dt_frame_gather(int32_t batch, const int64_t* idx, const void* frames, int32
   if (frame_kind == 1)
     frame_gather_kernel<<<grid, kFrameThreads, 0, (hipStream_t)stream>>>(
         idx, static_cast<const uint8_t*>(frames), hw, k, obs_ptr, next_ptr, action, reward, done,
-        obs, nxt, act, rew, notdone);
+        obs, nxt, act, rew, notdone, weights, w);
   else
     frame_gather_kernel<<<grid, kFrameThreads, 0, (hipStream_t)stream>>>(
         idx, static_cast<const float*>(frames), hw, k, obs_ptr, next_ptr, action, reward, done,
-        obs, nxt, act, rew, notdone);
+        obs, nxt, act, rew, notdone, weights, w);
   return hipGetLastError() == hipSuccess ? DT_OK : DT_E_HIP;
 }
 

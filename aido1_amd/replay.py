@@ -284,13 +284,19 @@ class ReplayBuffer:
                     st['done'].index_select(0, idxes))
         return tuple(st[name].index_select(0, idxes) for name in FIELDS)
 
-    def gather_into(self, idxes, out):
+    def gather_into(self, idxes, out, weights=None):
         """_encode_sample(idxes) written straight into a trainer's inputs `out`
         (DDPGTrainer.static_inputs: obs / nxt float32 channels_last [b, k, h, w],
         act [b, 2], rew [b, 1], notdone [b, 1]): one dt_frame_gather launch with
-        the frame store on the GPU (include/dtreplay.h), torch copies otherwise."""
+        the frame store on the GPU (include/dtreplay.h), torch copies otherwise.
+        weights (float64 [b], sample_indices' importance weights) go into
+        out['w'] ([b, 1], a trainer built with importance_weights=True) in the
+        same launch (dt_frame_gather_w)."""
         st = self.storage
         b = idxes.shape[0]
+        with_w = weights is not None and 'w' in out
+        if with_w and (weights.numel() != b or out['w'].numel() != b):
+            raise ValueError('gather_into: one weight per index')
         if (self.frames is not None and self.frames.is_cuda and out['obs'].dtype == torch.float32
                 and out['obs'].is_contiguous(memory_format=torch.channels_last)
                 and out['nxt'].is_contiguous(memory_format=torch.channels_last)
@@ -300,12 +306,23 @@ class ReplayBuffer:
             hw = self.frames[0].numel()
             idxes = idxes.contiguous()
             kind = 1 if self.frames.dtype == torch.uint8 else 0
-            rc = _lib.lib().dt_frame_gather(
-                b, idxes.data_ptr(), self.frames.data_ptr(), kind, hw, k, st['obs_ptr'].data_ptr(),
-                st['next_ptr'].data_ptr(), st['action'].data_ptr(), st['reward'].data_ptr(),
-                st['done'].data_ptr(), out['obs'].data_ptr(), out['nxt'].data_ptr(),
-                out['act'].data_ptr(), out['rew'].data_ptr(), out['notdone'].data_ptr(),
-                ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+            # the weights ride in the same launch; any other dtype is a torch copy
+            fused_w = (with_w and weights.dtype == torch.float64 and weights.is_cuda
+                       and out['w'].dtype == torch.float32 and out['w'].is_contiguous())
+            if with_w and not fused_w:
+                out['w'].copy_(weights.reshape(-1, 1))
+            args = (b, idxes.data_ptr(), self.frames.data_ptr(), kind, hw, k,
+                    st['obs_ptr'].data_ptr(), st['next_ptr'].data_ptr(), st['action'].data_ptr(),
+                    st['reward'].data_ptr(), st['done'].data_ptr(), out['obs'].data_ptr(),
+                    out['nxt'].data_ptr(), out['act'].data_ptr(), out['rew'].data_ptr(),
+                    out['notdone'].data_ptr())
+            stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            if fused_w:
+                weights = weights.contiguous()
+                rc = _lib.lib().dt_frame_gather_w(*args, weights.data_ptr(), out['w'].data_ptr(),
+                                                  stream)
+            else:
+                rc = _lib.lib().dt_frame_gather(*args, stream)
             if rc != 0:
                 raise _lib.DtError('dt_frame_gather failed (%d)' % rc)
             return out
@@ -315,6 +332,8 @@ class ReplayBuffer:
         out['act'].copy_(act)
         out['rew'].copy_(rew.reshape(-1, 1))
         out['notdone'].copy_((~done.bool()).reshape(-1, 1))
+        if with_w:
+            out['w'].copy_(weights.reshape(-1, 1))
         return out
 
     def uniforms(self, batch_size):

@@ -52,6 +52,7 @@ import torch
 
 from aido1_amd.actor import ConfigActor, ConfigCritic
 from aido1_amd.episodes import EpisodeBook
+from aido1_amd.explore import create_decay_fn
 from aido1_amd.guard import Guard
 from aido1_amd.replay import PrioritizedReplayBuffer, ReplayBuffer
 from aido1_amd.rollout import ActorRollout
@@ -60,17 +61,35 @@ from aido1_amd.trainer import DDPGTrainer
 PRIORITY_EPS = 1e-6
 
 
+def beta_schedule(training_config, beta_decay=None):
+    """The prioritized replay's beta as a function of the update count:
+    the constant training.beta, or beta_decay = {'type': ..., 'args': {...}}
+    (the form of the config's actor_train_decay entries, explore.create_decay_fn)
+    capped at 1 -- full correction; the sampler rejects beta <= 0 itself."""
+    if beta_decay is None:
+        beta = training_config['beta']
+        return lambda step: beta
+    fn = create_decay_fn(beta_decay['type'], **beta_decay['args'])
+    return lambda step: min(float(fn(step)), 1.0)
+
+
 class TrainLoop:
     def __init__(self, config, n_envs=4096, maps=('small_loop', 'zigzag'), device=0, seed=1234,
                  env_id_base=0, buffer_size=None, prioritized=True, batch_size=None,
                  updates_per_step=1, refresh_every=1, obs_dtype=None, actor_dtype=torch.float32,
                  actor_mode='reference', masks=False, graph=True, overlap=False, n_exploit=None,
-                 save_dir=None, log_dir=None, poll_every=0, check_every=0, frames='index'):
+                 save_dir=None, log_dir=None, poll_every=0, check_every=0, frames='index',
+                 importance_weights=False, beta_decay=None):
         t = config['training']
+        if importance_weights and not prioritized:
+            raise ValueError('importance_weights needs prioritized=True (the weights are the '
+                             'prioritized replay\'s)')
         self.config = config
         self.device = torch.device('cuda', device)
         self.batch_size = int(batch_size or t['batch_size'])
         self.beta = t['beta']
+        self.beta_at = beta_schedule(t, beta_decay)
+        self.importance_weights = bool(importance_weights)
         self.reward_modified = t.get('reward_modified', True)
         self.updates_per_step = updates_per_step
         self.refresh_every = refresh_every
@@ -80,7 +99,8 @@ class TrainLoop:
         # one non-finite guard for every stage of the loop (guard.py, check())
         self.guard = Guard(self.device)
         self.trainer = DDPGTrainer(config, actor, critic, device=self.device, graph=graph,
-                                   guard=self.guard)
+                                   guard=self.guard,
+                                   importance_weights=self.importance_weights)
         self.rollout = ActorRollout(config, n_envs, maps=maps, device=device, seed=seed,
                                     env_id_base=env_id_base, actor=self.trainer.actor,
                                     dtype=actor_dtype, masks=masks, actor_mode=actor_mode,
@@ -218,15 +238,20 @@ class TrainLoop:
         self.rollout.load_exploit_actor(self.trainer.target_actor)
 
     def _update(self):
+        if self.prioritized:
+            self.beta = self.beta_at(self.updates)
         if self.prioritized and self.trainer.dtype == torch.float32:
             # the sampled rows gathered straight into the update's inputs
             # (one dt_frame_gather launch, replay.gather_into)
-            idx, _w = self.replay.sample_indices(self.batch_size, self.beta)
-            self.replay.gather_into(idx, self.trainer.static_inputs(self.batch_size))
+            # (the weights too, into the 'w' only an importance_weights trainer has)
+            idx, w = self.replay.sample_indices(self.batch_size, self.beta)
+            self.replay.gather_into(idx, self.trainer.static_inputs(self.batch_size),
+                                    weights=w if self.importance_weights else None)
             self.metrics, info = self.trainer.update_prepared()
         elif self.prioritized:
-            obs, act, rew, nxt, done, _w, idx = self.replay.sample(self.batch_size, self.beta)
-            self.metrics, info = self.trainer.update((obs, act, rew, nxt, done))
+            obs, act, rew, nxt, done, w, idx = self.replay.sample(self.batch_size, self.beta)
+            self.metrics, info = self.trainer.update(
+                (obs, act, rew, nxt, done), weights=w if self.importance_weights else None)
         else:
             obs, act, rew, nxt, done = self.replay.sample(self.batch_size)
             self.metrics, info = self.trainer.update((obs, act, rew, nxt, done))

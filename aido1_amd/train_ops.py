@@ -772,6 +772,61 @@ def mse_loss(a, b):
     return F.mse_loss(a, b)
 
 
+class _LossW(torch.autograd.Function):
+    """dt_loss_w: mean(w * (a - b) ** 2) (kind 0) or mean(w * smooth_l1(a, b))
+    (kind 2), w the prioritized replay's importance weights (None: ones).  One
+    launch forward, one backward (gradient for `a` only: b is the detached
+    target, w the sampler's output)."""
+
+    @staticmethod
+    def forward(ctx, a, b, w, kind):
+        a, b = a.contiguous(), b.contiguous()
+        w = w.contiguous() if w is not None else None
+        loss = torch.empty((), device=a.device)
+        rc = _lib.lib().dt_loss_w(kind, a.numel(), a.data_ptr(), b.data_ptr(),
+                                  w.data_ptr() if w is not None else None, loss.data_ptr(),
+                                  torch.cuda.current_stream(a.device).cuda_stream)
+        if rc != 0:
+            raise _lib.DtError('dt_loss_w failed (%d)' % rc)
+        ctx.kind = kind
+        ctx.save_for_backward(a, b, w)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b, w = ctx.saved_tensors
+        g = g.contiguous()
+        da = torch.empty_like(a)
+        rc = _lib.lib().dt_loss_w_bwd(ctx.kind, a.numel(), a.data_ptr(), b.data_ptr(),
+                                      w.data_ptr() if w is not None else None, g.data_ptr(),
+                                      da.data_ptr(),
+                                      torch.cuda.current_stream(a.device).cuda_stream)
+        if rc != 0:
+            raise _lib.DtError('dt_loss_w_bwd failed (%d)' % rc)
+        return da, None, None, None
+
+
+_LOSS_W_KINDS = {'mse_loss': 0, 'smooth_l1_loss': 2}
+
+
+def weighted_loss(a, b, w, kind):
+    """The critic loss under importance weights, (w * loss_i).mean(): kind
+    'mse_loss' is (w * (a - b) ** 2).mean(), 'smooth_l1_loss' is
+    (w * F.smooth_l1_loss(a, b, reduction='none')).mean(); w None is ones.
+    One launch each way on the GPU (b and w without gradient)."""
+    if kind not in _LOSS_W_KINDS:
+        raise ValueError('weighted_loss: kind must be one of %s' % (tuple(_LOSS_W_KINDS),))
+    ts = (a, b) if w is None else (a, b, w)
+    if _loss_applicable(*ts) and not any(t.requires_grad for t in ts[1:]):
+        return _LossW.apply(a, b.detach(), None if w is None else w.detach(),
+                            _LOSS_W_KINDS[kind])
+    if kind == 'mse_loss':
+        terms = (a - b) ** 2
+    else:
+        terms = F.smooth_l1_loss(a, b, reduction='none')
+    return (terms if w is None else w * terms).mean()
+
+
 def neg_mean(a):
     """-1.0 * torch.mean(a) (the actor loss) in one launch each way on the GPU."""
     if _loss_applicable(a):

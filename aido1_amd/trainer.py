@@ -94,7 +94,7 @@ def _nullctx():
 class DDPGTrainer:
     def __init__(self, config, actor, critic, target_actor=None, target_critic=None,
                  device=None, sync_grads=None, bucket_mb=16, graph=False, warmup=3,
-                 conv_search=True, guard=None):
+                 conv_search=True, guard=None, importance_weights=False):
         t = config['training']
         self.config = config
         self.gamma, self.tau = float(t['gamma']), float(t['tau'])
@@ -113,6 +113,9 @@ class DDPGTrainer:
             m.to(memory_format=torch.channels_last)
             m.train()                           # managers.py:264-268 _prime_model
         self.graph = bool(graph) and self.device.type == 'cuda'
+        # the critic loss weighted by the prioritized replay's importance
+        # weights (buffers.py:225-233): an input 'w' beside the batch
+        self.importance_weights = bool(importance_weights)
         # an unknown kind raises NotImplementedError in make_optimizer
         self.actor_optim = make_optimizer(t['optimizer'], self.actor.parameters(), self.graph,
                                           self.device)
@@ -152,7 +155,7 @@ class DDPGTrainer:
     def _tensor(self, x, dtype=None):
         return torch.as_tensor(x, device=self.device).to(dtype or self.dtype)
 
-    def _inputs(self, train_data):
+    def _inputs(self, train_data, weights=None):
         observations, actions, rewards, next_observations, dones = train_data
         cl = torch.channels_last
         x = {'obs': self._tensor(observations).contiguous(memory_format=cl),
@@ -160,6 +163,11 @@ class DDPGTrainer:
              'act': self._tensor(actions),
              'rew': self._tensor(rewards).reshape(-1, 1),
              'notdone': (~self._tensor(dones, torch.bool).reshape(-1, 1)).to(self.dtype)}
+        if self.importance_weights:
+            x['w'] = (torch.ones_like(x['rew']) if weights is None
+                      else self._tensor(weights).reshape(-1, 1))
+            if x['w'].shape != x['rew'].shape:
+                raise ValueError('weights: one per batch row')
         if not self.graph:
             self._in = x
         elif self._in is None:
@@ -180,6 +188,8 @@ class DDPGTrainer:
             self._in = {'obs': z(batch, *obs_shape).contiguous(memory_format=cl),
                         'nxt': z(batch, *obs_shape).contiguous(memory_format=cl),
                         'act': z(batch, 2), 'rew': z(batch, 1), 'notdone': z(batch, 1)}
+            if self.importance_weights:
+                self._in['w'] = torch.ones(batch, 1, device=self.device, dtype=self.dtype)
         if self._in['obs'].shape[0] != batch:
             raise ValueError('graph mode needs a fixed batch shape')
         return self._in
@@ -319,7 +329,10 @@ class DDPGTrainer:
         x = self._in
         self.guard.tick()
         self._drop_open()
-        self.guard.scan('batch', x['obs'], x['act'], x['rew'], x['nxt'])
+        if self.importance_weights:
+            self.guard.scan('batch', x['obs'], x['act'], x['rew'], x['nxt'], x['w'])
+        else:
+            self.guard.scan('batch', x['obs'], x['act'], x['rew'], x['nxt'])
         # the targets' forward (target actor -> target critic on next_obs) and
         # the critic's forward on obs are independent: two streams, so their
         # batch-64 kernels (a few CUs each) run side by side -- in a HIP graph
@@ -350,7 +363,10 @@ class DDPGTrainer:
                 self.guard.scan('target', self._y)
         y_predicted = self.critic(x['obs'], x['act'])
         self._join(side, self._y)
-        if self.critic_loss_kind == 'mse_loss':
+        if self.importance_weights:
+            critic_loss = train_ops.weighted_loss(y_predicted, self._y, x['w'],
+                                                  self.critic_loss_kind)
+        elif self.critic_loss_kind == 'mse_loss':
             critic_loss = train_ops.mse_loss(y_predicted, self._y)
         else:
             critic_loss = F.smooth_l1_loss(y_predicted, self._y)
@@ -427,12 +443,17 @@ class DDPGTrainer:
             if isinstance(opt, DeviceStep):
                 opt.finish_capture()
 
-    def update(self, train_data):
+    def update(self, train_data, weights=None):
         """train_data = (obs, actions, rewards, next_obs, dones), leading batch
         dimension (numpy or tensors).  Returns (metrics, info) like the
         reference; metric values are 0-dim device tensors (valid until the
-        next update in graph mode)."""
-        self._inputs(train_data)
+        next update in graph mode).  weights (importance_weights=True only):
+        the prioritized replay's importance weights, [b] or [b, 1], None for
+        ones; the critic loss becomes (w * loss_i).mean(), its metric
+        sqrt of that, and td_error stays the unweighted y - Q(s, a)."""
+        if weights is not None and not self.importance_weights:
+            raise ValueError('weights need DDPGTrainer(importance_weights=True)')
+        self._inputs(train_data, weights)
         return self.update_prepared()
 
     def update_prepared(self):

@@ -63,6 +63,22 @@ int dt_loss(int32_t kind, int32_t m, const float* a, const float* b, float* loss
 int dt_loss_bwd(int32_t kind, int32_t m, const float* a, const float* b, const float* g,
                 float* da, void* stream);
 
+/* The critic loss under prioritized replay's importance weights (the weights
+ * of PrioritizedReplayBuffer.sample, utils/buffers.py:225-233): the same one
+ * workgroup and float64 sum order as dt_loss, every float32 term times w[i]:
+ *   kind 0: loss = (1/m) sum w_i (a_i - b_i)^2
+ *   kind 2: loss = (1/m) sum w_i l(a_i - b_i), l torch's smooth-L1 at beta = 1:
+ *           0.5 d^2 if |d| < 1, else |d| - 0.5
+ * dt_loss_w_bwd: da = (2 / m) (a - b) g w (kind 0), (1 / m) l'(a - b) g w
+ * (kind 2; l'(d) = d if |d| < 1, else sign(d)).  w multiplies last, and
+ * w == NULL is all ones, so kind 0 with ones (or NULL) is dt_loss /
+ * dt_loss_bwd kind 0 bit for bit.  Any other kind (1, the actor loss, takes
+ * no weights) is DT_E_ARG.  w device f32 [m]; m >= 1. */
+int dt_loss_w(int32_t kind, int32_t m, const float* a, const float* b, const float* w,
+              float* loss, void* stream);
+int dt_loss_w_bwd(int32_t kind, int32_t m, const float* a, const float* b, const float* w,
+                  const float* g, float* da, void* stream);
+
 /* The tail's backward from dy (= dL/dy [m, n2], or dL/dh [m, n1] for one
  * layer) and the forward's h and y: any output may be NULL (not wanted).
  *   dx0 [m, k0], dx1 [m, k1], dw1 [n1, k0 + k1], db1 [n1], dw2 [n2, n1], db2 [n2] */

@@ -119,6 +119,17 @@ int dt_frame_gather(int32_t batch, const int64_t* idx, const void* frames, int32
                     const float* action, const double* reward, const uint8_t* done, float* obs,
                     float* nxt, float* act, float* rew, float* notdone, void* stream);
 
+/* dt_frame_gather plus the batch's importance weights in the same launch:
+ * w[b] = (float)weights[b], weights device f64 [batch] (dt_per_sample's
+ * weights_dev: indexed by batch position, not by slot), w device f32 [batch]
+ * (the trainer's static 'w' input).  Both NULL: dt_frame_gather; exactly one
+ * NULL: DT_E_ARG. */
+int dt_frame_gather_w(int32_t batch, const int64_t* idx, const void* frames, int32_t frame_kind,
+                      int64_t hw, int32_t k, const int32_t* obs_ptr, const int32_t* next_ptr,
+                      const float* action, const double* reward, const uint8_t* done, float* obs,
+                      float* nxt, float* act, float* rew, float* notdone, const double* weights,
+                      float* w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,10 @@
 """Diagnostic (GPU): the DDPG update alone (config.json networks with their
 dropout, batch 64, graph mode) on one synthetic batch, for a per-update kernel
 profile: rocprofv3 --kernel-trace --stats -- python3 tools/update_only.py
-OPTIMIZER=adam|adamw|sgd overrides the config's training.optimizer.  Prints the median update time over the timed updates."""
+OPTIMIZER=adam|adamw|sgd overrides the config's training.optimizer,
+CRITIC_LOSS=mse_loss|smooth_l1_loss its training.critic_loss; IS_WEIGHTS=1 builds
+the trainer with importance_weights=True and feeds fixed seeded weights in
+(0, 1] (the prioritized replay's, train_ops.weighted_loss).  Prints the median update time over the timed updates."""
 import json
 import os
 import sys
@@ -22,10 +25,14 @@ def main():
         cfg = json.load(f)
     if os.environ.get('OPTIMIZER'):      # adam | adamw | sgd (trainers.py:258-268)
         cfg['training']['optimizer'] = os.environ['OPTIMIZER']
+    if os.environ.get('CRITIC_LOSS'):
+        cfg['training']['critic_loss'] = os.environ['CRITIC_LOSS']
+    is_w = os.environ.get('IS_WEIGHTS', '0') == '1'
+    kw = {'importance_weights': True} if is_w else {}
     torch.manual_seed(0)
     dev = torch.device('cuda', 0)
     tr = DDPGTrainer(cfg, ConfigActor(cfg['model']['actor']), ConfigCritic(cfg['model']['critic']),
-                     device=dev, graph=True)
+                     device=dev, graph=True, **kw)
     for kv in filter(None, os.environ.get('TR_SET', '').split(',')):   # attr=0/1 on the trainer
         k, v = kv.split('=')
         setattr(tr, k, bool(int(v)))
@@ -36,8 +43,10 @@ def main():
              torch.rand(b, device=dev, generator=g),
              torch.rand(b, 3, 120, 160, device=dev, generator=g),
              torch.zeros(b, dtype=torch.bool, device=dev))
+    # 1 - u, u in [0, 1): weights in (0, 1]
+    ukw = {'weights': 1.0 - torch.rand(b, device=dev, generator=g)} if is_w else {}
     for _ in range(5):
-        tr.update(batch)
+        tr.update(batch, **ukw)
     torch.cuda.synchronize()
     def timed(fn):
         times = []
@@ -52,10 +61,10 @@ def main():
     ab = os.environ.get('AB_ATTR')       # e.g. split_target: A/B of a trainer switch, one box
     if ab:
         tr2 = DDPGTrainer(cfg, ConfigActor(cfg['model']['actor']),
-                          ConfigCritic(cfg['model']['critic']), device=dev, graph=True)
+                          ConfigCritic(cfg['model']['critic']), device=dev, graph=True, **kw)
         setattr(tr2, ab, not getattr(tr, ab))
         for _ in range(5):
-            tr2.update(batch)
+            tr2.update(batch, **ukw)
         res = {True: [], False: []}
         for _ in range(5):
             for t in (tr, tr2):
@@ -69,7 +78,7 @@ def main():
         for v in (True, False):
             print('%s=%s back to back: %s ms (median %.3f)'
                   % (ab, v, ' '.join('%.3f' % x for x in res[v]), float(np.median(res[v]))))
-    t_full = timed(lambda: tr.update(batch))
+    t_full = timed(lambda: tr.update(batch, **ukw))
     # the inputs already in the static buffers (TrainLoop: dt_frame_gather)
     t_prep = timed(tr.update_prepared)
     # back to back, as the training loop issues them (the host runs ahead of
@@ -92,8 +101,9 @@ def main():
     tr.check()
     print('update %.3f ms with the input conversion + copies, %.3f ms on prepared inputs '
           '(medians of %d, each synchronised); %.3f ms back to back (median of 5 means of %d, '
-          'host ahead)'
-          % (t_full, t_prep, n_up, t_b2b, n_up))
+          'host ahead); critic_loss %s, importance weights %s'
+          % (t_full, t_prep, n_up, t_b2b, n_up, cfg['training'].get('critic_loss', 'mse_loss'),
+             'on' if is_w else 'off'))
 
 
 if __name__ == '__main__':
