@@ -37,6 +37,9 @@ struct dt_handle {
   hipEvent_t render_done = nullptr;
   hipStream_t render_stream = nullptr;
   bool render_pending = false;
+  // dt_render_objects: the footprint records the render draws (0: none)
+  void* render_objs = nullptr;   // float [DT_MAX_RENDER_OBJECTS][DT_RENDER_OBJ_STRIDE]
+  int32_t n_render_objs = 0;
   std::string err;
 };
 

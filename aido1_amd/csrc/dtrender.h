@@ -33,7 +33,8 @@ constexpr uint32_t kPalette[PAL_N] = {
     rgb_pack(0, 0, 0),        // floor / outside the map
     rgb_pack(72, 132, 52),    // grass (any non-drivable tile)
     rgb_pack(56, 56, 60),     // road surface
-    rgb_pack(220, 30, 30),    // red stop line (never drawn: intersections carry no markings)
+    rgb_pack(220, 30, 30),    // red: an object's footprint (dt_render_objects; no stop lines:
+                              // intersections carry no markings)
     kYellowRgb,               // yellow centre line over floor / grass / road
     kYellowRgb,
     kYellowRgb,

@@ -333,6 +333,11 @@ struct RenderArgs {
   const uint8_t* fresh3;
   uint8_t* masks2;
   uint8_t* masks3;
+  // dt_render_objects: the map's object footprints, drawn by the kObj
+  // instantiations (two float4 a record: c0x, c0z, e1x, e1z | e2x, e2z,
+  // e1.e1, e2.e2), the same for every decision of a group
+  const float4* objs;
+  int32_t n_objs;
 };
 
 // ---- fused render kernel ----------------------------------------------------------
@@ -350,6 +355,12 @@ struct RenderArgs {
 //   0b  listed spans resolved a word at a time, OR-ed in, beside the markings
 //       drawn with Bresenham, OR-ed in (raster byte encoding, dtrender.h):
 //       order-free, so one pass
+//   0c  (kObj: dt_render_objects) the map's object footprints: one object per
+//       lane projected and culled by its pixel box, the ones in view listed;
+//       then four lanes per (listed object, row of its box) test the row
+//       span's pixel centres against the rectangle and store PAL_RED over
+//       whatever lies below (a plain byte store: every object writes the
+//       same value)
 //   1   every 16-pixel quad: neighbourhood uniformity of its 4 words;
 //       non-uniform words get a slot (the list)
 //   2a  listed words: SWAR 3-channel Sobel -> entry (mag | dir); the slot + 1
@@ -391,7 +402,7 @@ constexpr int kListCap = 1984;      // listed words kept in LDS (loop_empty: med
 constexpr int kWeakCap = 512;
 constexpr int kSegRecs = 2176;     // uint2 segment records (phase 0, over the entry area)
 constexpr int kSpillHalves = 5 * NW;         // global spill per env: 4 entries + 1 list word
-enum { kNSpan = 0, kNSeg = 1, kNList = 2, kNQuad = 3, kNWeak = 4, kNCnt = 8 };
+enum { kNSpan = 0, kNSeg = 1, kNList = 2, kNQuad = 3, kNWeak = 4, kNObj = 5, kNCnt = 8 };
 // A work entry (16 bits a pixel of a listed word).  Sobel (2a) writes mag | dir;
 // NMS (2b) reads its own word's dir, then writes the entry back as
 //   mag (0-10) | dilated colour bits of the pixel (11-13) | CAND (14) | EDGE (15)
@@ -412,6 +423,10 @@ struct RenderLds {
       uint2 seg[kSegRecs];         // phase 0: visible segments (yellow up, white down)
       uint16_t qlist[NQ];          // phase 0: the non-uniform background spans
     } p;
+    struct {                       // object phase (kObj; p is dead, w not yet written):
+      float4 q[2 * DT_MAX_RENDER_OBJECTS];  // the records of the objects in view
+      uint2 box[DT_MAX_RENDER_OBJECTS];     // their pixel boxes: r0 | r1 << 16, c0 | c1 << 16
+    } o;
   } u;
   uint16_t weak[kWeakCap];
   uint32_t pal_swar[PAL_N];
@@ -425,6 +440,7 @@ struct RenderLds {
 };
 static_assert(sizeof(RenderLds) <= 163840 / 4, "four render workgroups per CU");
 static_assert(sizeof(((RenderLds*)0)->u.p) <= sizeof(((RenderLds*)0)->u.w), "phase-0 lists");
+static_assert(sizeof(((RenderLds*)0)->u.o) <= sizeof(((RenderLds*)0)->u.w), "object list");
 // segments projected in one round (loads issued at entry): 4 per lane, and
 // their records must fit the record area
 constexpr int kMarkFast = 4 * kRenderThreads < kSegRecs ? 4 * kRenderThreads : kSegRecs;
@@ -1246,8 +1262,95 @@ __device__ __forceinline__ void sched_exit(const RenderArgs& a, RenderLds& S, in
   }
 }
 
+// An object's record and pixel box for a camera, or false when the box (the
+// projected corners' bounds, kObjMargin pixels wider: the projection and the
+// per-pixel test round differently by far less) misses the frame.  The box is
+// a cull only: draw_objects decides every pixel with the exact test.
+constexpr float kObjMargin = 2.0f;
+__device__ inline bool object_box(const View& V, float4 qa, float4 qb, uint2& box) {
+  float cmin = 1e30f, cmax = -1e30f, rmin = 1e30f, rmax = -1e30f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {   // c0, c0 + e1, c0 + e1 + e2, c0 + e2
+    const float px = (qa.x + (k == 1 || k == 2 ? qa.z : 0.0f)) + (k >= 2 ? qb.x : 0.0f);
+    const float pz = (qa.y + (k == 1 || k == 2 ? qa.w : 0.0f)) + (k >= 2 ? qb.y : 0.0f);
+    const float ax = px - V.cx, az = pz - V.cz;   // project_seg's arithmetic
+    const float fa = ax * V.dirx + az * V.dirz, la = ax * V.rx + az * V.rz;
+    const float c = la * kInvRes + 79.5f, r = 119.5f - fa * kInvRes;
+    cmin = fminf(cmin, c);
+    cmax = fmaxf(cmax, c);
+    rmin = fminf(rmin, r);
+    rmax = fmaxf(rmax, r);
+  }
+  cmin = floorf(cmin - kObjMargin);
+  cmax = ceilf(cmax + kObjMargin);
+  rmin = floorf(rmin - kObjMargin);
+  rmax = ceilf(rmax + kObjMargin);
+  // (a NaN bound fails every test: culled, as the per-pixel test would reject)
+  if (!(cmax >= 0.0f && cmin <= (float)(W - 1) && rmax >= 0.0f && rmin <= (float)(H - 1)))
+    return false;
+  const uint32_t c0 = (uint32_t)fmaxf(cmin, 0.0f), c1 = (uint32_t)fminf(cmax, (float)(W - 1));
+  const uint32_t r0 = (uint32_t)fmaxf(rmin, 0.0f), r1 = (uint32_t)fminf(rmax, (float)(H - 1));
+  box = make_uint2(r0 | (r1 << 16), c0 | (c1 << 16));
+  return true;
+}
+
+// Phase 0c.  A pixel is an object's iff its centre's world point (tile_f's)
+// lies in the closed footprint rectangle: with d = point - c0,
+// 0 <= d.e1 <= e1.e1 and 0 <= d.e2 <= e2.e2, in float32 without contraction
+// (tests/render_objects_ref.py restates it).  Ends with the barrier phase 1
+// needs.
+__device__ __forceinline__ void draw_objects(const RenderArgs& a, RenderLds& S, const View& V) {
+  const int tid = opaque_tid();
+  constexpr int T = kRenderThreads;
+  for (int o0 = 0; o0 < a.n_objs; o0 += T) {
+    const int o = o0 + tid;
+    float4 qa, qb;
+    uint2 box;
+    bool vis = false;
+    if (o < a.n_objs) {
+      qa = a.objs[2 * o];
+      qb = a.objs[2 * o + 1];
+      vis = object_box(V, qa, qb, box);
+    }
+    const int slot = wave_slot1(&S.cnt[kNObj], vis);
+    if (vis) {   // slot < n_objs <= DT_MAX_RENDER_OBJECTS (the host checks)
+      S.u.o.q[2 * slot] = qa;
+      S.u.o.q[2 * slot + 1] = qb;
+      S.u.o.box[slot] = box;
+    }
+  }
+  __syncthreads();
+  uint8_t* const pix = reinterpret_cast<uint8_t*>(S.img);
+  // an item: a listed object, a frame row (rows outside its box drop out),
+  // one of kObjParts equal pieces of the box's columns (neighbouring lanes)
+  constexpr int kObjParts = 4;
+  const int items = S.cnt[kNObj] * (H * kObjParts);
+  for (int i = tid; i < items; i += T) {
+    const int j = i / (H * kObjParts), k = i - j * (H * kObjParts);
+    const int r = k / kObjParts, part = k - r * kObjParts;
+    const uint2 box = S.u.o.box[j];
+    if (r < (int)(box.x & 0xFFFFu) || r > (int)(box.x >> 16)) continue;
+    const float4 qa = S.u.o.q[2 * j], qb = S.u.o.q[2 * j + 1];
+    const float f = (119.5f - (float)r) * kRes;
+    const float bx = V.cx + f * V.dirx, bz = V.cz + f * V.dirz;
+    const int cb = (int)(box.y & 0xFFFFu), ce = (int)(box.y >> 16);
+    const int per = (ce - cb + kObjParts) / kObjParts;   // ceil((ce - cb + 1) / kObjParts)
+    const int c0 = cb + part * per, c1 = min(c0 + per - 1, ce);
+    // a plain loop: unrolled or vectorised, its copies' temporaries spill
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+    for (int c = c0; c <= c1; ++c) {
+      const float l = ((float)c - 79.5f) * kRes;
+      const float wx = bx + l * V.rx, wz = bz + l * V.rz;
+      const float dx = wx - qa.x, dz = wz - qa.y;
+      const float s = dx * qa.z + dz * qa.w, t = dx * qb.x + dz * qb.y;
+      if (s >= 0.0f && s <= qb.z && t >= 0.0f && t <= qb.w) pix[r * W + c] = PAL_RED;
+    }
+  }
+  __syncthreads();
+}
+
 // One env of render_kernel.
-template <bool kIdx, bool kBigR>
+template <bool kIdx, bool kBigR, bool kObj>
 __device__ __forceinline__ void render_env(const RenderArgs& a, RenderLds& S, int e, int half,
                                            int vi
 #ifdef DTSIM_EARLY_MARKS
@@ -1407,6 +1510,7 @@ __device__ __forceinline__ void render_env(const RenderArgs& a, RenderLds& S, in
     }
   }
   __syncthreads();
+  if (kObj) draw_objects(a, S, V);
   RENT(6);
   RENDER_STOP(2);
 
@@ -1517,8 +1621,9 @@ __device__ __forceinline__ void render_env(const RenderArgs& a, RenderLds& S, in
 #define DTSIM_RENDER_WPE 8
 #endif
 // kIdx: palette-byte frames (a.index) instead of grey floats; kBigR: a
-// dilation radius of 2-3.  Both are fixed for a launch: the host picks.
-template <bool kIdx, bool kBigR>
+// dilation radius of 2-3; kObj: the object footprints are drawn (phase 0c).
+// All are fixed for a launch: the host picks.
+template <bool kIdx, bool kBigR, bool kObj>
 __global__ __launch_bounds__(kRenderThreads) __attribute__((amdgpu_waves_per_eu(DTSIM_RENDER_WPE))) void
 render_kernel(RenderArgs a) {
   __shared__ __attribute__((aligned(16))) RenderLds S;
@@ -1595,7 +1700,7 @@ render_kernel(RenderArgs a) {
       if (tid < kNCnt) S.cnt[tid] = 0;
       __syncthreads();
     }
-    render_env<kIdx, kBigR>(a, S, e, half0 + vi, vi
+    render_env<kIdx, kBigR, kObj>(a, S, e, half0 + vi, vi
 #ifdef DTSIM_EARLY_MARKS
                , mq
 #endif
@@ -1971,6 +2076,9 @@ void dt_render_free(dt_handle* h) {
   h->render_sched = nullptr;
   if (h->render_done) (void)hipEventDestroy(h->render_done);
   h->render_done = nullptr;
+  if (h->render_objs) (void)hipFree(h->render_objs);
+  h->render_objs = nullptr;
+  h->n_render_objs = 0;
 }
 
 extern "C" {
@@ -2137,8 +2245,15 @@ static int render_launch(dt_handle* h, const dt_render_io* io, const dt_render_i
   }
   const int grid = DTSIM_RENDER_SEQ ? h->n : a.parts * h->n;
   const bool big_r = a.line.dil_r >= 2;
-  auto* kern = a.index ? (big_r ? render_kernel<true, true> : render_kernel<true, false>)
-                       : (big_r ? render_kernel<false, true> : render_kernel<false, false>);
+  a.objs = (const float4*)h->render_objs;
+  a.n_objs = h->n_render_objs;
+  decltype(&render_kernel<false, false, false>) kern;
+  if (a.n_objs > 0)
+    kern = a.index ? (big_r ? render_kernel<true, true, true> : render_kernel<true, false, true>)
+                   : (big_r ? render_kernel<false, true, true> : render_kernel<false, false, true>);
+  else
+    kern = a.index ? (big_r ? render_kernel<true, true, false> : render_kernel<true, false, false>)
+                   : (big_r ? render_kernel<false, true, false> : render_kernel<false, false, false>);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, a);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -2149,6 +2264,37 @@ static int render_launch(dt_handle* h, const dt_render_io* io, const dt_render_i
     h->render_stream = (hipStream_t)stream;
     h->render_pending = true;
   }
+  return DT_OK;
+}
+
+int dt_render_objects(dt_handle* h, const float* recs, int32_t n) {
+  if (!h) return DT_E_ARG;
+  if (n < 0 || n > DT_MAX_RENDER_OBJECTS) {
+    h->err = "dt_render_objects: n must be in 0..256";
+    return DT_E_ARG;
+  }
+  if (n > 0 && !recs) {
+    h->err = "dt_render_objects: recs is null";
+    return DT_E_ARG;
+  }
+  for (int i = 0; i < n * DT_RENDER_OBJ_STRIDE; ++i)
+    if (!isfinite(recs[i])) {
+      h->err = "dt_render_objects: record " + std::to_string(i / DT_RENDER_OBJ_STRIDE) +
+               " holds a non-finite value";
+      return DT_E_ARG;
+    }
+  DevGuard dg(h->device);
+  // launches in flight read the records: wait for them (synchronous, as dt_seed)
+  HIP_OR_FAIL(h, hipDeviceSynchronize());
+  if (n > 0) {
+    // one buffer for the handle's life, of the largest size: a launch captured
+    // into a graph keeps a valid pointer whatever is uploaded later
+    const size_t rec = DT_RENDER_OBJ_STRIDE * sizeof(float);
+    if (!h->render_objs)
+      HIP_OR_FAIL(h, hipMalloc(&h->render_objs, DT_MAX_RENDER_OBJECTS * rec));
+    HIP_OR_FAIL(h, hipMemcpy(h->render_objs, recs, (size_t)n * rec, hipMemcpyHostToDevice));
+  }
+  h->n_render_objs = n;
   return DT_OK;
 }
 

@@ -67,7 +67,8 @@ class GpuBatch:
     plus a 1-slot render (RGB raster) for the observations."""
 
     def __init__(self, n_envs, map_name='loop_empty', seed=0, device=None, env_id_base=0,
-                 max_steps=500001, accept_start_angle_deg=4, frame_skip=1, frame_rate=30):
+                 max_steps=500001, accept_start_angle_deg=4, frame_skip=1, frame_rate=30,
+                 draw_objects=False):
         import torch
         from aido1_amd.config import EnvConfig
         from aido1_amd.render import RenderOutput
@@ -79,7 +80,8 @@ class GpuBatch:
                         action_mode='wheels', auto_reset=False)
         self.torch = torch
         self.n = n_envs
-        self.env = VecEnv(n_envs, seed=seed, device=device, config=cfg, env_id_base=env_id_base)
+        self.env = VecEnv(n_envs, seed=seed, device=device, config=cfg, env_id_base=env_id_base,
+                          draw_objects=draw_objects)
         self.dev = self.env.device
         self.out = StepOutput(n_envs, self.dev)
         self.render = RenderOutput(n_envs, self.dev, slots=1, rgb=True, masks=False)
@@ -274,8 +276,11 @@ def main(argv=None):
     p.add_argument('--map', default='loop_empty')
     p.add_argument('--device', type=int, default=0)
     p.add_argument('--seed', type=int, default=0)
+    p.add_argument('--draw-objects', action='store_true',
+                   help='draw the map\'s static objects into the observations')
     a = p.parse_args(argv)
-    srv = EnvServer(GpuBatch(a.n_envs, map_name=a.map, seed=a.seed, device=a.device),
+    srv = EnvServer(GpuBatch(a.n_envs, map_name=a.map, seed=a.seed, device=a.device,
+                             draw_objects=a.draw_objects),
                     host=a.host, port_start=a.port).start()
     print('serving %d envs on %s:%d-%d' % (a.n_envs, a.host, a.port, a.port + a.n_envs - 1),
           flush=True)

@@ -251,6 +251,22 @@ class TileMap:
         return np.array(recs, np.float64).reshape(-1, 4)
 
     @property
+    def render_table(self):
+        """[M, 8] float32 footprint records of every object, spawn_table's set
+        (dt_render_objects, include/dtsim.h): corner 0 (x, z), e1 = corner 1 -
+        corner 0, e2 = corner 3 - corner 0, e1.e1, e2.e2 -- computed in
+        float64 from MapObject.corners (the rectangle the collision test uses;
+        not norms: a square footprint's eigenvector axes are arbitrary) and
+        rounded once."""
+        recs = []
+        for o in (self.objects or []):
+            c = np.asarray(o.corners, np.float64)
+            e1, e2 = c[1] - c[0], c[3] - c[0]
+            recs.append([c[0, 0], c[0, 1], e1[0], e1[1], e2[0], e2[1],
+                         e1[0] * e1[0] + e1[1] * e1[1], e2[0] * e2[0] + e2[1] * e2[1]])
+        return np.array(recs, np.float64).reshape(-1, 8).astype(np.float32)
+
+    @property
     def drivable(self):
         return np.nonzero(self.kind > 0)[0]
 

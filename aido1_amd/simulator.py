@@ -69,7 +69,7 @@ class Simulator:
                  camera_width=640, camera_height=480, accept_start_angle_deg=60,
                  full_transparency=False, distortion=False, frame_skip=1, draw_curve=False,
                  draw_bbox=False, robot_speed=None, frame_rate=30, device=None, env_id=0,
-                 **unsupported):
+                 draw_objects=False, **unsupported):
         if domain_rand:
             raise NotImplementedError('domain randomisation is not on the hot path '
                                       '(launch_env passes domain_rand=0, env.py:11)')
@@ -84,7 +84,8 @@ class Simulator:
             cfg = cfg.replace(robot_speed=robot_speed)
         self.config = cfg
         self._seed = 0 if seed is None else int(seed)
-        self._env = VecEnv(1, seed=self._seed, device=device, config=cfg, env_id_base=env_id)
+        self._env = VecEnv(1, seed=self._seed, device=device, config=cfg, env_id_base=env_id,
+                           draw_objects=draw_objects)
         self._dev = self._env.device
         self._out = RenderOutput(1, self._dev, slots=1, rgb=True, masks=False)
         self._act = torch.zeros(1, 2, dtype=torch.float32, device=self._dev)

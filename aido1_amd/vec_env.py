@@ -53,10 +53,15 @@ class VecEnv:
       config: EnvConfig; defaults reproduce launch_env() + config.json's wrapper.
       env_id_base: global id of env 0 (multi-GPU sharding: rank * n_envs), so
         shards draw disjoint spawn streams.
+      draw_objects: draw the map's static objects into the observation
+        (dt_render_objects: each object's footprint, filled red; build-defined,
+        the upstream meshes are absent).  Off by default: the frame then shows
+        tiles and lane markings only, as it always has.  No effect on a map
+        without objects.
     """
 
     def __init__(self, n_envs, map_name=None, seed=123, device=None, config=None,
-                 env_id_base=0):
+                 env_id_base=0, draw_objects=False):
         self.config = config or EnvConfig()
         if map_name is not None:
             self.config = self.config.replace(map_name=map_name)
@@ -87,6 +92,12 @@ class VecEnv:
                                self.n, device, ctypes.byref(h))
         _lib.check(self._L, None, rc, 'dt_create')
         self._h = h
+        self.draw_objects = bool(draw_objects)
+        table = np.ascontiguousarray(self.map.render_table, np.float32)
+        if self.draw_objects and len(table):   # (a map without objects: nothing to draw)
+            rc = self._L.dt_render_objects(self._h, table.ctypes.data_as(ctypes.c_void_p),
+                                           len(table))
+            _lib.check(self._L, self._h, rc, 'dt_render_objects')
         self.seed(seed)
         self.out = StepOutput(self.n, self.device)
         self._reset_obs = torch.zeros(self.n, 2, dtype=torch.float32, device=self.device)

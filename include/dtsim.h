@@ -17,7 +17,7 @@
  *     Pointers documented "host" are ordinary host memory.
  *   - All device work is enqueued on the given stream (hipStream_t passed as
  *     void*; NULL = the default stream).  Only dt_get_state / dt_set_state /
- *     dt_seed synchronise.
+ *     dt_seed / dt_render_objects synchronise.
  *   - One handle per (process, GPU).  Calls on one handle are not thread-safe.
  */
 #ifndef AIDO1_AMD_DTSIM_H
@@ -58,7 +58,9 @@ extern "C" {
                             13: dtactor.h dt_actor_head_x3_drop,
                                 dt_actor_head_f16_drop;
                             14: dttrain.h dt_adamw, dt_sgd (the reference's
-                                other two optimisers as device steps) */
+                                other two optimisers as device steps);
+                                dt_render_objects (additive: the map's objects
+                                drawn into the observation, off by default) */
 
 /* error codes */
 #define DT_OK 0
@@ -313,6 +315,38 @@ int dt_render2(dt_handle* h, const dt_render_io* io_a, const dt_render_io* io_b,
  * equals dt_render(io_a), dt_render(io_b), dt_render(io_c) in that order. */
 int dt_render3(dt_handle* h, const dt_render_io* io_a, const dt_render_io* io_b,
                const dt_render_io* io_c, void* stream);
+
+/* Draw the map's static objects into every later render of this handle (opt-in;
+ * a new handle draws none, as before).  Upstream Simulator.render_obs draws
+ * each object's mesh; the meshes are absent here, so an object's look is
+ * build-defined and parity with upstream is not pinned: it is its footprint
+ * rectangle (the corners _collision tests, DT_OBJ_CORNERS) filled with the
+ * palette's red (byte 3: RGB 220, 30, 30), over whatever background or lane
+ * marking lies below.  Every object of the map is drawn, collidable or not
+ * (the set of dt_map.spawn_objects).  The frame, the red mask, Canny's edges,
+ * the grey and index rings and the rgb output all see it, in dt_render,
+ * dt_render2 and dt_render3 alike (the same records for every decision).
+ *   recs  host [n, DT_RENDER_OBJ_STRIDE] f32, a record per object, computed in
+ *         float64 (aido1_amd/maps.py TileMap.render_table) and rounded once:
+ *         [0..1] corner 0 (x, z); [2..3] e1 = corner 1 - corner 0; [4..5] e2 =
+ *         corner 3 - corner 0; [6] e1.e1; [7] e2.e2
+ *   n     objects, 0..DT_MAX_RENDER_OBJECTS; 0 switches the drawing off
+ * A pixel (row r, column c) is an object's iff its centre's world point lies in
+ * the closed rectangle, all in float32, each operation rounded (no fused
+ * multiply-add), in this order (V: the camera at the pose, float32: position
+ * (cx, cz) = pose + camera_forward_dist * dir, dir = (cos a, -sin a), right =
+ * (sin a, cos a)):
+ *   f  = (119.5f - r) * 0.01f;  l = (c - 79.5f) * 0.01f
+ *   wx = (V.cx + f * V.dirx) + l * V.rx;  wz = (V.cz + f * V.dirz) + l * V.rz
+ *   dx = wx - q0;  dz = wz - q1
+ *   s  = dx * q2 + dz * q3;  t = dx * q4 + dz * q5
+ *   inside = s >= 0 && s <= q6 && t >= 0 && t <= q7
+ * Synchronous (waits for the device, then uploads into a buffer the handle
+ * owns).  DT_E_ARG, with dt_last_error set and nothing changed, for n < 0,
+ * n > DT_MAX_RENDER_OBJECTS, recs NULL with n > 0, or a non-finite value. */
+#define DT_RENDER_OBJ_STRIDE 8
+#define DT_MAX_RENDER_OBJECTS 256
+int dt_render_objects(dt_handle* h, const float* recs, int32_t n);
 
 /* Diagnostics of that dispatch order (synchronises): launches so far, each
  * env's last recorded cost (shader cycles) and the order the next launch

@@ -34,7 +34,11 @@ def main():
     n = int(os.environ.get('ENVS', '4096'))
     K = int(os.environ.get('K', '40'))
     dev = torch.device('cuda', 0)
-    env = VecEnv(n, seed=1234, device=0, config=EnvConfig(map_name=os.environ.get('MAP', 'loop_empty')))
+    # DRAW=1: the map's objects drawn into the frames (VecEnv(draw_objects=True));
+    # with MAP=loop_obstacles, against DRAW=0 on the same map, the cost of drawing
+    draw = os.environ.get('DRAW', '0') == '1'
+    env = VecEnv(n, seed=1234, device=0, config=EnvConfig(map_name=os.environ.get('MAP', 'loop_empty')),
+                 draw_objects=draw)
     env.reset()
     acts = torch.rand(K + 10, n, 2, device=dev)
     outs = [StepOutput(n, dev, lanepos=False, tile=False) for _ in range(K + 10)]
@@ -52,7 +56,8 @@ def main():
     ms0 = timed(lambda i: env.render_into(ro, pose=poses[10 + i]), K)
     ms1 = timed(lambda i: env.render_into(ro, pose=poses[10]), K)
     byt = 153624 * n
-    print('render, %d envs, %d recorded decisions (fresh %.1f %%):' % (n, K, 100 * fr))
+    print('render, %d envs, %d recorded decisions (fresh %.1f %%)%s:'
+          % (n, K, 100 * fr, ', objects drawn' if draw else ''))
     for name, m in (('fresh = done', ms), ('no fresh', ms0), ('one pose, no fresh', ms1)):
         print('  %-20s mean %.4f ms  min %.4f  max %.4f  -> %.1f %% of 8 TB/s (single-slot bytes)'
               % (name, m.mean(), m.min(), m.max(), 100 * byt / (m.mean() * 1e-3) / 8e12))
