@@ -363,6 +363,16 @@ def exported_symbols():
     return sorted(names)
 
 
+def call(name, *args, L=None):
+    """lib().<name>(*args) for an entry point that returns a status and takes
+    no handle: non-zero raises DtError naming it (L: a bound library other
+    than lib()'s).  Not a ctypes errcheck: L.dt_* called directly still
+    returns its code."""
+    rc = getattr(L if L is not None else lib(), name)(*args)
+    if rc != 0:
+        raise DtError('%s failed (%d)' % (name, rc))
+
+
 def check(L, handle, rc, what):
     if rc != 0:
         msg = L.dt_last_error(handle)

@@ -546,10 +546,8 @@ class FusedActor(nn.Module):
                 self.w0frag.device)
             ent = cache[key] = (table, keep, len(rows), max(r.count for r in rows))
         table, _keep, n, most = ent
-        rc = _lib.lib().dt_refresh_copy(n, table.data_ptr(), most,
-                                        torch.cuda.current_stream(table.device).cuda_stream)
-        if rc != 0:
-            raise _lib.DtError('dt_refresh_copy failed (%d)' % rc)
+        _lib.call('dt_refresh_copy', n, table.data_ptr(), most,
+                  torch.cuda.current_stream(table.device).cuda_stream)
 
     def _refresh(self, actor):
         """The eager refresh: reference mode executes _refresh_pairs with
@@ -613,13 +611,9 @@ class FusedActor(nn.Module):
             n, c, h, w = x.shape
             assert x.is_contiguous(memory_format=torch.channels_last)
             dt = {torch.bfloat16: 0, torch.float32: 1, torch.float16: 2}[x.dtype]
-            L = _lib.lib()
-            rc = L.dt_sample_norm(x.data_ptr(), x.data_ptr(), n, h * w, c,
-                                  self.gamma[i].data_ptr(), self.beta[i].data_ptr(),
-                                  self.eps[i], 0.01, dt,
-                                  torch.cuda.current_stream(x.device).cuda_stream)
-            if rc != 0:
-                raise _lib.DtError('dt_sample_norm failed (%d)' % rc)
+            _lib.call('dt_sample_norm', x.data_ptr(), x.data_ptr(), n, h * w, c,
+                      self.gamma[i].data_ptr(), self.beta[i].data_ptr(), self.eps[i], 0.01, dt,
+                      torch.cuda.current_stream(x.device).cuda_stream)
             return x
         x = F.leaky_relu(x).float()
         mean = x.mean((2, 3), keepdim=True)
@@ -871,12 +865,11 @@ class FusedActor(nn.Module):
                 if a.mode == 'reference' and a.p_drop > 0:
                     x = F.dropout(x, a.p_drop, training=True)
                 torch.addmm(a.b1, x, a.w1.t(), out=h[sl])
-        rc = _lib.lib().dt_actor_head(
+        _lib.call(
+            'dt_actor_head',
             n, n0, k, h.data_ptr(), k, self.w2.data_ptr(), self.b2.data_ptr(), o.w2.data_ptr(),
             o.b2.data_ptr(), self._HEAD_CODES[self.head], 0.01, out.data_ptr(),
             ctypes.c_void_p(torch.cuda.current_stream(flat.device).cuda_stream))
-        if rc != 0:
-            raise _lib.DtError('dt_actor_head failed (%d)' % rc)
 
     def _drop_seed(self, p):
         """A fresh key for the head's folded dropout (one a call), from a
@@ -904,15 +897,13 @@ class FusedActor(nn.Module):
         fresh counter-based key."""
         p =self.p_drop if self.mode == 'reference' else 0.0
         n = flat.shape[0]
-        rc = getattr(_lib.lib(), entry)(
-            n, n0, FLAT, flat.data_ptr(), float(p), self._drop_seed(p),
+        _lib.call(
+            entry, n, n0, FLAT, flat.data_ptr(), float(p), self._drop_seed(p),
             getattr(self, w1).data_ptr(), self.b1.data_ptr(), self.w2.data_ptr(),
             self.b2.data_ptr(), getattr(o, w1).data_ptr(), o.b1.data_ptr(), o.w2.data_ptr(),
             o.b2.data_ptr(), self._HEAD_CODES[self.head], 0.01,
             self._head_work(n, flat.device).data_ptr(), out.data_ptr(),
             ctypes.c_void_p(torch.cuda.current_stream(flat.device).cuda_stream))
-        if rc != 0:
-            raise _lib.DtError('%s failed (%d)' % (entry, rc))
 
 
 def _take(src, idx):

@@ -66,7 +66,7 @@ class EpisodeTracker:
             self.ring.data_ptr(), self.capacity)
         self.read = 0        # records drained so far
         self.lost = 0        # records overwritten before a drain
-        self._L = _lib.lib()
+        _lib.lib()           # a missing library raises here, not at the first account()
 
     def account(self, reward, reward_mod, done, stream=None):
         """Enqueue one dt_episode_account over k = reward.numel() / n decisions."""
@@ -79,11 +79,9 @@ class EpisodeTracker:
         if m == 0 or m % self.n:
             raise ValueError('%d entries is not k * %d' % (m, self.n))
         st = stream if stream is not None else torch.cuda.current_stream(self.device)
-        rc = self._L.dt_episode_account(self.n, m // self.n, reward.data_ptr(),
-                                        reward_mod.data_ptr(), done.data_ptr(),
-                                        ctypes.byref(self.state), ctypes.c_void_p(st.cuda_stream))
-        if rc != 0:
-            raise _lib.DtError('dt_episode_account failed (%d)' % rc)
+        _lib.call('dt_episode_account', self.n, m // self.n, reward.data_ptr(),
+                  reward_mod.data_ptr(), done.data_ptr(), ctypes.byref(self.state),
+                  ctypes.c_void_p(st.cuda_stream))
 
     def reset(self):
         """Every env starts a new episode (an explicit reset): the running sums

@@ -207,15 +207,13 @@ class FusedExplore:
         if self.every_second_random:
             coin = torch.rand(n, dtype=torch.float64, device=dev, generator=generator)
             uni = torch.rand(n, 2, device=dev, generator=generator)
-        rc = self.L.dt_explore(n, ao.data_ptr(), normals.data_ptr(),
-                               coin.data_ptr() if coin is not None else None,
-                               uni.data_ptr() if uni is not None else None,
-                               self.ou.x.data_ptr(), self.ou.n_steps.data_ptr(), episode.data_ptr(),
-                               self.ce.cl.data_ptr(), self.ce.max_step.data_ptr(),
-                               self.ids.data_ptr(), self.params, actions.data_ptr(),
-                               torch.cuda.current_stream(dev).cuda_stream)
-        if rc != 0:
-            raise _lib.DtError('dt_explore failed (%d)' % rc)
+        _lib.call('dt_explore', n, ao.data_ptr(), normals.data_ptr(),
+                  coin.data_ptr() if coin is not None else None,
+                  uni.data_ptr() if uni is not None else None,
+                  self.ou.x.data_ptr(), self.ou.n_steps.data_ptr(), episode.data_ptr(),
+                  self.ce.cl.data_ptr(), self.ce.max_step.data_ptr(), self.ids.data_ptr(),
+                  self.params, actions.data_ptr(), torch.cuda.current_stream(dev).cuda_stream,
+                  L=self.L)
         return actions
 
     def done(self, done, episode, actions=None):
@@ -225,8 +223,6 @@ class FusedExplore:
         n, dev = self.ou.n, self.ou.x.device
         assert done.dtype == torch.uint8 and done.numel() == n and done.is_contiguous()
         tm = int(actions is not None and self.tanh)
-        rc = self.L.dt_explore_done(n, done.data_ptr(), self.ou.x.data_ptr(), episode.data_ptr(),
-                                    actions.data_ptr() if tm else None, tm,
-                                    torch.cuda.current_stream(dev).cuda_stream)
-        if rc != 0:
-            raise _lib.DtError('dt_explore_done failed (%d)' % rc)
+        _lib.call('dt_explore_done', n, done.data_ptr(), self.ou.x.data_ptr(), episode.data_ptr(),
+                  actions.data_ptr() if tm else None, tm,
+                  torch.cuda.current_stream(dev).cuda_stream, L=self.L)

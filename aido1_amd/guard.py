@@ -89,11 +89,9 @@ class Guard:
                     raise ValueError('guard scan: dense float32/float64 tensors only')
                 a.p, a.count, a.bit = t.data_ptr(), t.numel(), bit
                 a.dtype = 0 if t.dtype == torch.float32 else 1
-            rc = _lib.lib().dt_guard_scan(len(part), ctypes.cast(arr, ctypes.c_void_p),
-                                          self.words.data_ptr(), ctypes.c_void_p(
-                torch.cuda.current_stream(self.device).cuda_stream))
-            if rc != 0:
-                raise _lib.DtError('dt_guard_scan failed (%d)' % rc)
+            _lib.call('dt_guard_scan', len(part), ctypes.cast(arr, ctypes.c_void_p),
+                      self.words.data_ptr(),
+                      ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
 
     def _raise_cpu(self, bit, bad):
         w = self.words

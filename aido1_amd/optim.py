@@ -347,11 +347,9 @@ class DeviceAdam(DeviceStep, torch.optim.Adam):
         from aido1_amd import _lib
         t = self._table_for(rows)
         b1, b2 = g['betas']
-        rc = _lib.lib().dt_adam(t.n_chunks, t.tensors.data_ptr(), t.chunks.data_ptr(),
-                                self._step_t.data_ptr(), g['lr'].data_ptr(), float(b1), float(b2),
-                                float(g['eps']), self._counter.data_ptr(), *self._launch_tail())
-        if rc != 0:
-            raise _lib.DtError('dt_adam failed (%d)' % rc)
+        _lib.call('dt_adam', t.n_chunks, t.tensors.data_ptr(), t.chunks.data_ptr(),
+                  self._step_t.data_ptr(), g['lr'].data_ptr(), float(b1), float(b2),
+                  float(g['eps']), self._counter.data_ptr(), *self._launch_tail())
         return None
 
 
@@ -408,12 +406,10 @@ class DeviceAdamW(DeviceStep, AdamW):
         g = self.param_groups[0]
         t = self._table_for(rows)
         b1, b2 = g['betas']
-        rc = _lib.lib().dt_adamw(t.n_chunks, t.tensors.data_ptr(), t.chunks.data_ptr(),
-                                 self._step_t.data_ptr(), g['lr'].data_ptr(), float(b1), float(b2),
-                                 float(g['eps']), float(g['weight_decay']),
-                                 self._counter.data_ptr(), *self._launch_tail())
-        if rc != 0:
-            raise _lib.DtError('dt_adamw failed (%d)' % rc)
+        _lib.call('dt_adamw', t.n_chunks, t.tensors.data_ptr(), t.chunks.data_ptr(),
+                  self._step_t.data_ptr(), g['lr'].data_ptr(), float(b1), float(b2),
+                  float(g['eps']), float(g['weight_decay']), self._counter.data_ptr(),
+                  *self._launch_tail())
         return None
 
 
@@ -447,11 +443,9 @@ class DeviceSGD(DeviceStep, torch.optim.SGD):
             return self._host_step(closure, grads)
         from aido1_amd import _lib
         t = self._table_for(rows)
-        rc = _lib.lib().dt_sgd(t.n_chunks, t.tensors.data_ptr(), t.chunks.data_ptr(),
-                               g['lr'].data_ptr(), float(g['momentum']),
-                               float(g['weight_decay']), *self._launch_tail())
-        if rc != 0:
-            raise _lib.DtError('dt_sgd failed (%d)' % rc)
+        _lib.call('dt_sgd', t.n_chunks, t.tensors.data_ptr(), t.chunks.data_ptr(),
+                  g['lr'].data_ptr(), float(g['momentum']), float(g['weight_decay']),
+                  *self._launch_tail())
         return None
 
 
@@ -484,11 +478,9 @@ class SoftUpdate:
         if t is None or t.key != MultiTensorTable.key_of(rows):
             t = self._tables[key] = MultiTensorTable(rows, rows[0][0].device)
         from aido1_amd import _lib
-        rc = _lib.lib().dt_soft_update(t.n_chunks, t.tensors.data_ptr(), t.chunks.data_ptr(),
-                                       float(tau), ctypes.c_void_p(torch.cuda.current_stream(
-                                           rows[0][0].device).cuda_stream))
-        if rc != 0:
-            raise _lib.DtError('dt_soft_update failed (%d)' % rc)
+        _lib.call('dt_soft_update', t.n_chunks, t.tensors.data_ptr(), t.chunks.data_ptr(),
+                  float(tau),
+                  ctypes.c_void_p(torch.cuda.current_stream(rows[0][0].device).cuda_stream))
 
 
 def make_optimizer(kind, params, capturable=False, device=None):

@@ -233,7 +233,6 @@ class ReplayBuffer:
         b = self._fblock % (self.frames.shape[0] // n)
         dn = fields['done']
         if self.device.type == 'cuda':
-            L = _lib.lib()
             if (not newest[0].is_contiguous() or ring.dtype != self.frames.dtype
                     or ring.dtype not in (torch.float32, torch.uint8)):
                 raise ValueError('frame store: the ring must hold float32 or uint8 frames, '
@@ -242,14 +241,11 @@ class ReplayBuffer:
             sz = ring.element_size()
             fe, stride = newest[0].numel() * sz // 4, newest.stride(0) * sz // 4
             with torch.cuda.device(self.device):
-                rc = L.dt_frame_add(n, fe, newest.data_ptr(), stride,
-                                    self.frames[b * n].data_ptr(), k, self._stack.data_ptr(),
-                                    dn.view(torch.uint8).data_ptr(), b * n,
-                                    st['obs_ptr'][p].data_ptr(), st['next_ptr'][p].data_ptr(),
-                                    ctypes.c_void_p(torch.cuda.current_stream(self.device)
-                                                    .cuda_stream))
-            if rc != 0:
-                raise _lib.DtError('dt_frame_add failed (%d)' % rc)
+                _lib.call('dt_frame_add', n, fe, newest.data_ptr(), stride,
+                          self.frames[b * n].data_ptr(), k, self._stack.data_ptr(),
+                          dn.view(torch.uint8).data_ptr(), b * n, st['obs_ptr'][p].data_ptr(),
+                          st['next_ptr'][p].data_ptr(),
+                          ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
             self._fblock += 1
         else:   # CPU tensors (tests): the same bookkeeping in torch
             row0 = self._frame_block(newest)
@@ -319,12 +315,10 @@ class ReplayBuffer:
             stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             if fused_w:
                 weights = weights.contiguous()
-                rc = _lib.lib().dt_frame_gather_w(*args, weights.data_ptr(), out['w'].data_ptr(),
-                                                  stream)
+                _lib.call('dt_frame_gather_w', *args, weights.data_ptr(), out['w'].data_ptr(),
+                          stream)
             else:
-                rc = _lib.lib().dt_frame_gather(*args, stream)
-            if rc != 0:
-                raise _lib.DtError('dt_frame_gather failed (%d)' % rc)
+                _lib.call('dt_frame_gather', *args, stream)
             return out
         obs, act, rew, nxt, done = self._encode_sample(idxes)
         out['obs'].copy_(obs)

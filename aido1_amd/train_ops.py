@@ -21,6 +21,14 @@ from the convolution output z.  The modules, parameters and state_dict are
 the unchanged torch ones; ``applicable`` / ``trunk_len`` /
 ``linear_applicable`` say when the kernels replace them.
 
+Every launch goes through ``_lib.call`` (a non-zero status raises DtError
+naming the entry point).  What the Functions share is written once, each
+taking the stream it runs on: ``_bn_bwd`` (dt_bn_leaky_bwd, every conv
+Function's first backward launch), then ``_conv_grads`` (the weight gradient,
+always dt_upd_conv_wgrad_bn -- without a BatchNorm hand-off the same launch as
+dt_upd_conv_wgrad -- then the input gradient); ``_mlp_prep`` for dt_mlp_fwd
+and dt_mlp_fwd_td; ``_Loss`` for both loss entry point pairs.
+
 Streams: every BatchNorm module owns its kernels' scratch (the partials and
 work buffers, ``_dt_part`` / ``_dt_work``), so ONE module must not be
 forwarded on two streams at once.  The trainer's two-stream stages
@@ -80,23 +88,38 @@ def attach_guard(module, guard):
             m._dt_guard = guard
 
 
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _updates(bn):
+    """How often this forward moves bn's running statistics (running_updates)."""
+    return int(getattr(bn, '_dt_updates', 1))
+
+
+def _bn_bwd(bn, dy, z, bias, mi, gamma, slope, s):
+    """dt_bn_leaky_bwd of block `bn` on stream s: (dz, g), g[3, C] the bias,
+    gamma and beta gradients."""
+    dz = torch.empty_like(z)
+    g = torch.empty(3, C, device=z.device)      # dbias, dgamma, dbeta
+    _lib.call('dt_bn_leaky_bwd', z.numel() // C, dy.data_ptr(), z.data_ptr(), bias.data_ptr(),
+              mi.data_ptr(), gamma.data_ptr(), slope, dz.data_ptr(), g[0].data_ptr(),
+              g[1].data_ptr(), g[2].data_ptr(), _work(bn, 'bwd', z.device).data_ptr(),
+              _guard(bn), s)
+    return dz, g
+
+
 class _BnLeaky(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z, bias, gamma, beta, bn, slope):
-        L = _lib.lib()
         m = z.numel() // C
         y = torch.empty_like(z)
         mi = torch.empty(2 * C, device=z.device)
-        nbt = bn.num_batches_tracked
-        rc = L.dt_bn_leaky_fwd(m, z.data_ptr(), bias.data_ptr(), slope, gamma.data_ptr(),
-                               beta.data_ptr(), bn.eps, bn.momentum, bn.running_mean.data_ptr(),
-                               bn.running_var.data_ptr(),
-                               nbt.data_ptr() if nbt is not None else None,
-                               int(getattr(bn, '_dt_updates', 1)), None,
-                               y.data_ptr(), mi.data_ptr(), _work(bn, 'fwd', z.device).data_ptr(),
-                               _guard(bn), _stream(z.device))
-        if rc != 0:
-            raise _lib.DtError('dt_bn_leaky_fwd failed (%d)' % rc)
+        _lib.call('dt_bn_leaky_fwd', m, z.data_ptr(), bias.data_ptr(), slope, gamma.data_ptr(),
+                  beta.data_ptr(), bn.eps, bn.momentum, bn.running_mean.data_ptr(),
+                  bn.running_var.data_ptr(), _ptr(bn.num_batches_tracked), _updates(bn), None,
+                  y.data_ptr(), mi.data_ptr(), _work(bn, 'fwd', z.device).data_ptr(),
+                  _guard(bn), _stream(z.device))
         # the activation is recomputed from z and bias in the backward (never stored)
         ctx.save_for_backward(z, bias, mi, gamma)
         ctx.bn, ctx.slope = bn, slope
@@ -106,16 +129,7 @@ class _BnLeaky(torch.autograd.Function):
     def backward(ctx, dy):
         z, bias, mi, gamma = ctx.saved_tensors
         dy = dy.contiguous(memory_format=torch.channels_last)
-        L = _lib.lib()
-        dz = torch.empty_like(z)
-        g = torch.empty(3, C, device=z.device)      # dbias, dgamma, dbeta
-        rc = L.dt_bn_leaky_bwd(z.numel() // C, dy.data_ptr(), z.data_ptr(), bias.data_ptr(),
-                               mi.data_ptr(), gamma.data_ptr(), ctx.slope, dz.data_ptr(),
-                               g[0].data_ptr(), g[1].data_ptr(), g[2].data_ptr(),
-                               _work(ctx.bn, 'bwd', z.device).data_ptr(), _guard(ctx.bn),
-                               _stream(z.device))
-        if rc != 0:
-            raise _lib.DtError('dt_bn_leaky_bwd failed (%d)' % rc)
+        dz, g = _bn_bwd(ctx.bn, dy, z, bias, mi, gamma, ctx.slope, _stream(z.device))
         return dz, g[0], g[1], g[2], None, None
 
 
@@ -151,6 +165,30 @@ def upd_conv_applicable(x, conv):
             in UPD_CONV_LAYERS)
 
 
+def _conv_grads(x, w, dz, st, want_dw, want_dx, hand, s, torch_dx_only=False):
+    """The gradients of conv2d(x, w, stride st) from dz on stream s: (dx, dw),
+    None where not wanted.  dw: dt_upd_conv_wgrad_bn, x normalised while
+    staged when `hand` (the DtUpdBn of the block that made x) is given.  dx:
+    dt_upd_conv_dgrad; the observation layer (C_in != C, no kernel: its input
+    never needs one here) and torch_dx_only go through torch."""
+    n, cin, ih, iw = x.shape
+    dims = (cin, w.shape[2], st, n, ih, iw)
+    dx = dw = None
+    if want_dw:
+        work = torch.empty(int(_lib.lib().dt_upd_wgrad_work_floats(*dims)), device=x.device)
+        dw = torch.empty_like(w)
+        _lib.call('dt_upd_conv_wgrad_bn', *dims, x.data_ptr(),
+                  ctypes.byref(hand) if hand is not None else None, dz.data_ptr(),
+                  dw.data_ptr(), work.data_ptr(), s)
+    if want_dx:
+        if torch_dx_only or cin != C:
+            dx = torch.nn.grad.conv2d_input(x.shape, w, dz, stride=st)
+        else:
+            dx = torch.empty_like(x)
+            _lib.call('dt_upd_conv_dgrad', *dims, dz.data_ptr(), w.data_ptr(), dx.data_ptr(), s)
+    return dx, dw
+
+
 class _UpdConv(torch.autograd.Function):
     """conv2d(x, w, stride) without bias on include/dtupd.h: NHWC f32, the
     weight in its channels_last memory ([co][kh][kw][ci]); backward = the
@@ -165,10 +203,8 @@ class _UpdConv(torch.autograd.Function):
         ks = w.shape[2]
         oh, ow = (ih - ks) // st + 1, (iw - ks) // st + 1
         z = torch.empty((n, C, oh, ow), device=x.device, dtype=x.dtype, memory_format=cl)
-        rc = _lib.lib().dt_upd_conv_fwd(cin, ks, st, n, ih, iw, x.data_ptr(), w.data_ptr(),
-                                        z.data_ptr(), _stream(x.device))
-        if rc != 0:
-            raise _lib.DtError('dt_upd_conv_fwd failed (%d)' % rc)
+        _lib.call('dt_upd_conv_fwd', cin, ks, st, n, ih, iw, x.data_ptr(), w.data_ptr(),
+                  z.data_ptr(), _stream(x.device))
         ctx.save_for_backward(x, w)
         ctx.st = st
         return z
@@ -176,30 +212,9 @@ class _UpdConv(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dz):
         x, w = ctx.saved_tensors
-        st = ctx.st
-        cl = torch.channels_last
-        dz = dz.contiguous(memory_format=cl)
-        n, cin, ih, iw = x.shape
-        ks = w.shape[2]
-        L = _lib.lib()
-        dx = dw = None
-        if ctx.needs_input_grad[1]:
-            work = torch.empty(int(L.dt_upd_wgrad_work_floats(cin, ks, st, n, ih, iw)),
-                               device=x.device)
-            dw = torch.empty_like(w)
-            rc = L.dt_upd_conv_wgrad(cin, ks, st, n, ih, iw, x.data_ptr(), dz.data_ptr(),
-                                     dw.data_ptr(), work.data_ptr(), _stream(x.device))
-            if rc != 0:
-                raise _lib.DtError('dt_upd_conv_wgrad failed (%d)' % rc)
-        if ctx.needs_input_grad[0]:
-            if cin != C:    # the observation layer: its input never needs one here
-                dx = torch.nn.grad.conv2d_input(x.shape, w, dz, stride=st)
-            else:
-                dx = torch.empty_like(x)
-                rc = L.dt_upd_conv_dgrad(cin, ks, st, n, ih, iw, dz.data_ptr(), w.data_ptr(),
-                                         dx.data_ptr(), _stream(x.device))
-                if rc != 0:
-                    raise _lib.DtError('dt_upd_conv_dgrad failed (%d)' % rc)
+        dz = dz.contiguous(memory_format=torch.channels_last)
+        dx, dw = _conv_grads(x, w, dz, ctx.st, ctx.needs_input_grad[1], ctx.needs_input_grad[0],
+                             None, _stream(x.device))
         return dx, dw, None
 
 
@@ -213,8 +228,8 @@ class _ConvBnLeaky(torch.autograd.Function):
     forward dt_upd_conv_fwd_bn (convolution + the batch statistics in its
     epilogue) and dt_bn_leaky_apply; backward dt_bn_leaky_bwd (BatchNorm,
     LeakyReLU and bias gradients), then the convolution's weight and input
-    gradients (dt_upd_conv_wgrad / _dgrad).  Four to five kernels each way
-    where MIOpen plus the tail ran eight or more."""
+    gradients (_conv_grads).  Four to five kernels each way where MIOpen plus
+    the tail ran eight or more."""
 
     @staticmethod
     def forward(ctx, x, w, bias, gamma, beta, bn, slope, st):
@@ -224,24 +239,17 @@ class _ConvBnLeaky(torch.autograd.Function):
         n, cin, ih, iw = x.shape
         ks = w.shape[2]
         oh, ow = (ih - ks) // st + 1, (iw - ks) // st + 1
-        L = _lib.lib()
         z = torch.empty((n, C, oh, ow), device=x.device, dtype=x.dtype, memory_format=cl)
         mi = torch.empty(2 * C, device=x.device)
-        nbt = bn.num_batches_tracked
         s = _stream(x.device)
-        rc = L.dt_upd_conv_fwd_bn(cin, ks, st, n, ih, iw, x.data_ptr(), w.data_ptr(),
-                                  bias.data_ptr(), slope, bn.eps, bn.momentum,
-                                  bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                                  nbt.data_ptr() if nbt is not None else None,
-                                  int(getattr(bn, '_dt_updates', 1)), z.data_ptr(), mi.data_ptr(),
-                                  _work(bn, 'upd', x.device).data_ptr(), _guard(bn), s)
-        if rc != 0:
-            raise _lib.DtError('dt_upd_conv_fwd_bn failed (%d)' % rc)
+        _lib.call('dt_upd_conv_fwd_bn', cin, ks, st, n, ih, iw, x.data_ptr(), w.data_ptr(),
+                  bias.data_ptr(), slope, bn.eps, bn.momentum, bn.running_mean.data_ptr(),
+                  bn.running_var.data_ptr(), _ptr(bn.num_batches_tracked), _updates(bn),
+                  z.data_ptr(), mi.data_ptr(), _work(bn, 'upd', x.device).data_ptr(),
+                  _guard(bn), s)
         y = torch.empty_like(z)
-        rc = L.dt_bn_leaky_apply(z.numel() // C, z.data_ptr(), bias.data_ptr(), slope,
-                                 mi.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), s)
-        if rc != 0:
-            raise _lib.DtError('dt_bn_leaky_apply failed (%d)' % rc)
+        _lib.call('dt_bn_leaky_apply', z.numel() // C, z.data_ptr(), bias.data_ptr(), slope,
+                  mi.data_ptr(), gamma.data_ptr(), beta.data_ptr(), y.data_ptr(), s)
         ctx.save_for_backward(x, w, z, bias, mi, gamma)
         ctx.bn, ctx.slope, ctx.st = bn, slope, st
         return y
@@ -249,51 +257,20 @@ class _ConvBnLeaky(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w, z, bias, mi, gamma = ctx.saved_tensors
-        cl = torch.channels_last
-        dy = dy.contiguous(memory_format=cl)
-        L = _lib.lib()
+        dy = dy.contiguous(memory_format=torch.channels_last)
         s = _stream(z.device)
-        dz = torch.empty_like(z)
-        g = torch.empty(3, C, device=z.device)      # dbias, dgamma, dbeta
-        rc = L.dt_bn_leaky_bwd(z.numel() // C, dy.data_ptr(), z.data_ptr(), bias.data_ptr(),
-                               mi.data_ptr(), gamma.data_ptr(), ctx.slope, dz.data_ptr(),
-                               g[0].data_ptr(), g[1].data_ptr(), g[2].data_ptr(),
-                               _work(ctx.bn, 'bwd', z.device).data_ptr(), _guard(ctx.bn), s)
-        if rc != 0:
-            raise _lib.DtError('dt_bn_leaky_bwd failed (%d)' % rc)
-        n, cin, ih, iw = x.shape
-        ks, st = w.shape[2], ctx.st
-        dx = dw = None
-        if ctx.needs_input_grad[1]:
-            work = torch.empty(int(L.dt_upd_wgrad_work_floats(cin, ks, st, n, ih, iw)),
-                               device=x.device)
-            dw = torch.empty_like(w)
-            rc = L.dt_upd_conv_wgrad(cin, ks, st, n, ih, iw, x.data_ptr(), dz.data_ptr(),
-                                     dw.data_ptr(), work.data_ptr(), s)
-            if rc != 0:
-                raise _lib.DtError('dt_upd_conv_wgrad failed (%d)' % rc)
-        if ctx.needs_input_grad[0]:
-            if cin != C:
-                dx = torch.nn.grad.conv2d_input(x.shape, w, dz, stride=st)
-            else:
-                dx = torch.empty_like(x)
-                rc = L.dt_upd_conv_dgrad(cin, ks, st, n, ih, iw, dz.data_ptr(), w.data_ptr(),
-                                         dx.data_ptr(), s)
-                if rc != 0:
-                    raise _lib.DtError('dt_upd_conv_dgrad failed (%d)' % rc)
+        dz, g = _bn_bwd(ctx.bn, dy, z, bias, mi, gamma, ctx.slope, s)
+        dx, dw = _conv_grads(x, w, dz, ctx.st, ctx.needs_input_grad[1], ctx.needs_input_grad[0],
+                             None, s)
         return dx, dw, g[0], g[1], g[2], None, None, None
 
 
 def _bn_handoff(bn, slope, part, parts, m, bias, gamma, beta, mi):
     """include/dtupd.h DtUpdBn for block `bn` (pointers into live tensors)."""
-    nbt = bn.num_batches_tracked
-    g = getattr(bn, '_dt_guard', None)
     return _lib.DtUpdBn(part.data_ptr(), int(parts), int(m), bias.data_ptr(), gamma.data_ptr(),
                         beta.data_ptr(), float(slope), float(bn.eps), float(bn.momentum),
                         bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                        nbt.data_ptr() if nbt is not None else None,
-                        int(getattr(bn, '_dt_updates', 1)), mi.data_ptr(),
-                        g.ptr() if g is not None else None)
+                        _ptr(bn.num_batches_tracked), _updates(bn), mi.data_ptr(), _guard(bn))
 
 
 def _part(bn, dev):
@@ -320,7 +297,6 @@ class _ConvTrunk(torch.autograd.Function):
     def forward(ctx, x, meta, *params):
         bns, slopes, strides = meta
         cl = torch.channels_last
-        L = _lib.lib()
         dev = x.device
         s = _stream(dev)
         x = x.contiguous(memory_format=cl)
@@ -336,12 +312,10 @@ class _ConvTrunk(torch.autograd.Function):
             z = torch.empty((n, C, oh, ow), device=dev, dtype=x.dtype, memory_format=cl)
             part = _part(bn, dev)
             parts = ctypes.c_int32(0)
-            rc = L.dt_upd_conv_fwd_part(cin, ks, st, n, ih, iw, cur.data_ptr(),
-                                        ctypes.byref(prev) if prev is not None else None,
-                                        ws[j].data_ptr(), bias.data_ptr(), slopes[j], z.data_ptr(),
-                                        part.data_ptr(), ctypes.byref(parts), s)
-            if rc != 0:
-                raise _lib.DtError('dt_upd_conv_fwd_part failed (%d)' % rc)
+            _lib.call('dt_upd_conv_fwd_part', cin, ks, st, n, ih, iw, cur.data_ptr(),
+                      ctypes.byref(prev) if prev is not None else None, ws[j].data_ptr(),
+                      bias.data_ptr(), slopes[j], z.data_ptr(), part.data_ptr(),
+                      ctypes.byref(parts), s)
             mi = torch.empty(2 * C, device=dev)
             prev = _bn_handoff(bn, slopes[j], part, parts.value, n * oh * ow, bias, gamma, beta,
                                mi)
@@ -350,10 +324,8 @@ class _ConvTrunk(torch.autograd.Function):
             cur = z
         # y in plain NCHW: the flatten after the trunk is a view, not a copy
         y = torch.empty(cur.shape, device=dev, dtype=cur.dtype)
-        rc = L.dt_upd_bn_finish(cur.numel() // C, cur.shape[2] * cur.shape[3], cur.data_ptr(),
-                                ctypes.byref(prev), y.data_ptr(), s)
-        if rc != 0:
-            raise _lib.DtError('dt_upd_bn_finish failed (%d)' % rc)
+        _lib.call('dt_upd_bn_finish', cur.numel() // C, cur.shape[2] * cur.shape[3],
+                  cur.data_ptr(), ctypes.byref(prev), y.data_ptr(), s)
         ctx.save_for_backward(x, *ws, *zs, *mis, *params)
         ctx.meta, ctx.k = meta, len(bns)
         return y
@@ -365,53 +337,26 @@ class _ConvTrunk(torch.autograd.Function):
         saved = ctx.saved_tensors
         x, ws, zs, mis, params = (saved[0], saved[1:1 + k], saved[1 + k:1 + 2 * k],
                                   saved[1 + 2 * k:1 + 3 * k], saved[1 + 3 * k:])
-        cl = torch.channels_last
-        L = _lib.lib()
         dev = x.device
         s = _stream(dev)
         grads = [None] * (4 * k)
-        dx = None
-        dyj = dy.contiguous(memory_format=cl)
+        dyj = dy.contiguous(memory_format=torch.channels_last)
         for j in range(k - 1, -1, -1):
             bias, gamma, beta = params[4 * j + 1: 4 * j + 4]
-            z = zs[j]
-            dz = torch.empty_like(z)
-            g = torch.empty(3, C, device=dev)      # dbias, dgamma, dbeta
-            rc = L.dt_bn_leaky_bwd(z.numel() // C, dyj.data_ptr(), z.data_ptr(), bias.data_ptr(),
-                                   mis[j].data_ptr(), gamma.data_ptr(), slopes[j], dz.data_ptr(),
-                                   g[0].data_ptr(), g[1].data_ptr(), g[2].data_ptr(),
-                                   _work(bns[j], 'bwd', dev).data_ptr(), _guard(bns[j]), s)
-            if rc != 0:
-                raise _lib.DtError('dt_bn_leaky_bwd failed (%d)' % rc)
+            dz, g = _bn_bwd(bns[j], dyj, zs[j], bias, mis[j], gamma, slopes[j], s)
             grads[4 * j + 1], grads[4 * j + 2], grads[4 * j + 3] = g[0], g[1], g[2]
-            xin = x if j == 0 else zs[j - 1]
-            n, cin, ih, iw = xin.shape
-            w, st = ws[j], strides[j]
-            ks = w.shape[2]
             hand = None
             if j > 0:
                 pb, pg, pbt = params[4 * j - 3: 4 * j]
                 hand = _bn_handoff(bns[j - 1], slopes[j - 1], _part(bns[j - 1], dev), 1, 1, pb,
                                    pg, pbt, mis[j - 1])
-            if ctx.needs_input_grad[2 + 4 * j]:
-                work = torch.empty(int(L.dt_upd_wgrad_work_floats(cin, ks, st, n, ih, iw)),
-                                   device=dev)
-                dw = torch.empty_like(w)
-                rc = L.dt_upd_conv_wgrad_bn(cin, ks, st, n, ih, iw, xin.data_ptr(),
-                                            ctypes.byref(hand) if hand is not None else None,
-                                            dz.data_ptr(), dw.data_ptr(), work.data_ptr(), s)
-                if rc != 0:
-                    raise _lib.DtError('dt_upd_conv_wgrad_bn failed (%d)' % rc)
-                grads[4 * j] = dw
-            if j > 0:
-                dyj = torch.empty_like(xin)
-                rc = L.dt_upd_conv_dgrad(cin, ks, st, n, ih, iw, dz.data_ptr(), w.data_ptr(),
-                                         dyj.data_ptr(), s)
-                if rc != 0:
-                    raise _lib.DtError('dt_upd_conv_dgrad failed (%d)' % rc)
-            elif ctx.needs_input_grad[0]:
-                dx = torch.nn.grad.conv2d_input(x.shape, w, dz, stride=st)
-        return (dx, None) + tuple(grads)
+            # inner blocks always pass a gradient down, on the kernel; the
+            # first one only if the trunk's input asks, and then through torch
+            dyj, grads[4 * j] = _conv_grads(x if j == 0 else zs[j - 1], ws[j], dz, strides[j],
+                                            ctx.needs_input_grad[2 + 4 * j],
+                                            j > 0 or ctx.needs_input_grad[0], hand, s,
+                                            torch_dx_only=j == 0)
+        return (dyj, None) + tuple(grads)
 
 
 # the chain kernels for runs of >= 2 blocks (False: block by block, for A/B runs)
@@ -495,21 +440,16 @@ class _UpdLinear(torch.autograd.Function):
         w = w.contiguous()
         m, k = x.shape
         n = w.shape[0]
-        L = _lib.lib()
         y = torch.empty(m, n, device=x.device, dtype=x.dtype)
-        work = torch.empty(int(L.dt_upd_linear_work_floats(m, n, k)), device=x.device)
+        work = torch.empty(int(_lib.lib().dt_upd_linear_work_floats(m, n, k)), device=x.device)
         act = slope is not None
         # the dropped input for the weight gradient (written by the forward)
         # (grads: autograd is recording -- Function.forward itself runs with it off)
         want = grads and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
         xd = torch.empty_like(x) if (u is not None and want) else None
-        rc = L.dt_upd_linear_fwd_drop(m, n, k, x.data_ptr(), u.data_ptr() if u is not None else None,
-                                      float(p), xd.data_ptr() if xd is not None else None,
-                                      w.data_ptr(), b.data_ptr(), int(act),
-                                      float(slope) if act else 0.0, y.data_ptr(), work.data_ptr(),
-                                      _stream(x.device))
-        if rc != 0:
-            raise _lib.DtError('dt_upd_linear_fwd_drop failed (%d)' % rc)
+        _lib.call('dt_upd_linear_fwd_drop', m, n, k, x.data_ptr(), _ptr(u), float(p), _ptr(xd),
+                  w.data_ptr(), b.data_ptr(), int(act), float(slope) if act else 0.0,
+                  y.data_ptr(), work.data_ptr(), _stream(x.device))
         ctx.save_for_backward(x if u is None else xd, w, y if act else None, u)
         ctx.slope, ctx.p = slope, float(p)
         return y
@@ -517,29 +457,23 @@ class _UpdLinear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         xs, w, yv, u = ctx.saved_tensors
-        yact = yv.data_ptr() if yv is not None else None
-        up = u.data_ptr() if u is not None else None
+        yact = _ptr(yv)
         slope = float(ctx.slope) if ctx.slope is not None else 0.0
         dy = dy.contiguous()
         m, k = dy.shape[0], w.shape[1]
         n = w.shape[0]
-        L = _lib.lib()
         s = _stream(dy.device)
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(m, k, device=dy.device, dtype=dy.dtype)
-            rc = L.dt_upd_linear_dgrad_drop(m, n, k, dy.data_ptr(), w.data_ptr(), yact, slope, up,
-                                            ctx.p, dx.data_ptr(), s)
-            if rc != 0:
-                raise _lib.DtError('dt_upd_linear_dgrad_drop failed (%d)' % rc)
+            _lib.call('dt_upd_linear_dgrad_drop', m, n, k, dy.data_ptr(), w.data_ptr(), yact,
+                      slope, _ptr(u), ctx.p, dx.data_ptr(), s)
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             dw = torch.empty_like(w)
             db = torch.empty(n, device=dy.device, dtype=dy.dtype)
             # xs: the input, or with a dropout the dropped input the forward wrote
-            rc = L.dt_upd_linear_wgrad(m, n, k, dy.data_ptr(), xs.data_ptr(), yact, slope,
-                                       dw.data_ptr(), db.data_ptr(), s)
-            if rc != 0:
-                raise _lib.DtError('dt_upd_linear_wgrad failed (%d)' % rc)
+            _lib.call('dt_upd_linear_wgrad', m, n, k, dy.data_ptr(), xs.data_ptr(), yact, slope,
+                      dw.data_ptr(), db.data_ptr(), s)
         return dx, dw, db, None, None, None, None
 
 
@@ -548,6 +482,8 @@ class _UpdLinear(torch.autograd.Function):
 # dropout takes the next slice; outside a pool (or past its end) a site draws
 # its own torch.rand.  The slices are static tensors, so a captured graph
 # replays the single draw (graph-safe Philox offsets) and the sites read it.
+# The trainer holds the pool on an ExitStack around its stages, so an update
+# that raises leaves none installed (tests/test_gpu_trainer.py).
 _DROP = {'pool': None, 'next': 0}
 FOLD_DROPOUT = True   # fold a dropout into the linear after it (A/B switch, tools/update_only.py)
 
@@ -636,10 +572,21 @@ def mlp_plan(seq, parts):
 
 
 def _mlp_struct(x0, x1, w1, b1, w2, b2, act1, act2, slope):
-    ptr = (lambda t: t.data_ptr() if t is not None else None)
     return _lib.DtMlp(x0.shape[0], x0.shape[1], x1.shape[1] if x1 is not None else 0,
                       w1.shape[0], w2.shape[0] if w2 is not None else 0, act1, act2, slope,
-                      w1.data_ptr(), ptr(b1), ptr(w2), ptr(b2))
+                      w1.data_ptr(), _ptr(b1), _ptr(w2), _ptr(b2))
+
+
+def _mlp_prep(x0, x1, w1, b1, w2, b2, meta):
+    """What a forward launch takes: the contiguous inputs and weights, the
+    DtMlp struct on them, and the hidden and output buffers (y None without a
+    second layer)."""
+    contig = (lambda t: t.contiguous() if t is not None else None)
+    x0, x1, w1, w2 = contig(x0), contig(x1), contig(w1), contig(w2)
+    p = _mlp_struct(x0, x1, w1, b1, w2, b2, *meta)
+    h = torch.empty(p.m, p.n1, device=x0.device)
+    y = torch.empty(p.m, p.n2, device=x0.device) if p.n2 else None
+    return x0, x1, w1, w2, p, h, y
 
 
 class _Mlp(torch.autograd.Function):
@@ -648,20 +595,9 @@ class _Mlp(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x0, x1, w1, b1, w2, b2, meta):
-        act1, act2, slope = meta
-        x0 = x0.contiguous()
-        x1 = x1.contiguous() if x1 is not None else None
-        w1 = w1.contiguous()
-        w2 = w2.contiguous() if w2 is not None else None
-        p = _mlp_struct(x0, x1, w1, b1, w2, b2, act1, act2, slope)
-        h = torch.empty(p.m, p.n1, device=x0.device)
-        y = torch.empty(p.m, p.n2, device=x0.device) if p.n2 else None
-        rc = _lib.lib().dt_mlp_fwd(ctypes.byref(p), x0.data_ptr(),
-                                   x1.data_ptr() if x1 is not None else None, h.data_ptr(),
-                                   y.data_ptr() if y is not None else None,
-                                   torch.cuda.current_stream(x0.device).cuda_stream)
-        if rc != 0:
-            raise _lib.DtError('dt_mlp_fwd failed (%d)' % rc)
+        x0, x1, w1, w2, p, h, y = _mlp_prep(x0, x1, w1, b1, w2, b2, meta)
+        _lib.call('dt_mlp_fwd', ctypes.byref(p), x0.data_ptr(), _ptr(x1), h.data_ptr(), _ptr(y),
+                  _stream(x0.device))
         ctx.meta = meta
         ctx.has = (x1 is not None, b1 is not None, w2 is not None, b2 is not None)
         ctx.save_for_backward(x0, x1, w1, b1, w2, b2, h, y)
@@ -670,21 +606,16 @@ class _Mlp(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x0, x1, w1, b1, w2, b2, h, y = ctx.saved_tensors
-        act1, act2, slope = ctx.meta
         need = ctx.needs_input_grad
         dy = dy.contiguous()
         new = (lambda t, want: torch.empty_like(t) if (want and t is not None) else None)
         dx0, dx1 = new(x0, need[0]), new(x1, need[1])
         dw1, db1 = new(w1, need[2]), new(b1, need[3])
         dw2, db2 = new(w2, need[4]), new(b2, need[5])
-        p = _mlp_struct(x0, x1, w1, b1, w2, b2, act1, act2, slope)
-        ptr = (lambda t: t.data_ptr() if t is not None else None)
-        rc = _lib.lib().dt_mlp_bwd(ctypes.byref(p), x0.data_ptr(), ptr(x1), h.data_ptr(), ptr(y),
-                                   dy.data_ptr(), ptr(dx0), ptr(dx1), ptr(dw1), ptr(db1),
-                                   ptr(dw2), ptr(db2),
-                                   torch.cuda.current_stream(dy.device).cuda_stream)
-        if rc != 0:
-            raise _lib.DtError('dt_mlp_bwd failed (%d)' % rc)
+        p = _mlp_struct(x0, x1, w1, b1, w2, b2, *ctx.meta)
+        _lib.call('dt_mlp_bwd', ctypes.byref(p), x0.data_ptr(), _ptr(x1), h.data_ptr(), _ptr(y),
+                  dy.data_ptr(), _ptr(dx0), _ptr(dx1), _ptr(dw1), _ptr(db1), _ptr(dw2),
+                  _ptr(db2), _stream(dy.device))
         return dx0, dx1, dw1, db1, dw2, db2, None
 
 
@@ -707,54 +638,54 @@ def mlp_td(parts, plan, rew, notdone, gamma):
     rew + (notdone * gamma) * y in one dt_mlp_fwd_td launch; returns the
     target [m, n_out] (no autograd: the target networks' pass)."""
     w1, b1, act1, w2, b2, act2, slope = plan
-    x0 = parts[0].contiguous()
-    x1 = parts[1].contiguous() if len(parts) == 2 else None
-    p = _mlp_struct(x0, x1, w1.contiguous(), b1, w2.contiguous() if w2 is not None else None, b2,
-                    act1, act2, slope)
-    dev = x0.device
-    h = torch.empty(p.m, p.n1, device=dev)
-    y = torch.empty(p.m, p.n2, device=dev) if p.n2 else None
-    target = torch.empty(p.m, p.n2 or p.n1, device=dev)
-    rc = _lib.lib().dt_mlp_fwd_td(ctypes.byref(p), x0.data_ptr(),
-                                  x1.data_ptr() if x1 is not None else None, h.data_ptr(),
-                                  y.data_ptr() if y is not None else None, rew.data_ptr(),
-                                  notdone.data_ptr(), float(gamma), target.data_ptr(),
-                                  torch.cuda.current_stream(dev).cuda_stream)
-    if rc != 0:
-        raise _lib.DtError('dt_mlp_fwd_td failed (%d)' % rc)
+    x0, x1, _, _, p, h, y = _mlp_prep(parts[0], parts[1] if len(parts) == 2 else None, w1, b1,
+                                      w2, b2, (act1, act2, slope))
+    target = torch.empty(p.m, p.n2 or p.n1, device=x0.device)
+    _lib.call('dt_mlp_fwd_td', ctypes.byref(p), x0.data_ptr(), _ptr(x1), h.data_ptr(), _ptr(y),
+              rew.data_ptr(), notdone.data_ptr(), float(gamma), target.data_ptr(),
+              _stream(x0.device))
     return target
 
 
-# ---- the DDPG losses (include/dthead.h dt_loss) ------------------------------------------
+# ---- the DDPG losses (include/dthead.h dt_loss, dt_loss_w) -------------------------------
+def _w_arg(entry, w):
+    """The weights' argument of a loss launch: only dt_loss_w has one (NULL: ones)."""
+    return (_ptr(w),) if entry == 'dt_loss_w' else ()
+
+
 class _Loss(torch.autograd.Function):
-    """kind 0: F.mse_loss(a, b) (mean); kind 1: -mean(a).  One launch forward,
-    one backward (gradient for `a` only: b is the detached target)."""
+    """One launch forward, one backward (gradient for `a` only: b is the
+    detached target, w the sampler's output), on the entry point pair `entry`
+    / `entry`_bwd:
+    dt_loss: kind 0 F.mse_loss(a, b) (mean); kind 1 -mean(a) (b None).
+    dt_loss_w: mean(w * (a - b) ** 2) (kind 0) or mean(w * smooth_l1(a, b))
+    (kind 2), w the prioritized replay's importance weights (None: ones)."""
 
     @staticmethod
-    def forward(ctx, a, b, kind):
+    def forward(ctx, a, b, w, kind, entry):
         a = a.contiguous()
         b = b.contiguous() if b is not None else None
+        w = w.contiguous() if w is not None else None
         loss = torch.empty((), device=a.device)
-        rc = _lib.lib().dt_loss(kind, a.numel(), a.data_ptr(),
-                                b.data_ptr() if b is not None else None, loss.data_ptr(),
-                                torch.cuda.current_stream(a.device).cuda_stream)
-        if rc != 0:
-            raise _lib.DtError('dt_loss failed (%d)' % rc)
-        ctx.kind = kind
-        ctx.save_for_backward(a, b)
+        _lib.call(entry, kind, a.numel(), a.data_ptr(), _ptr(b), *_w_arg(entry, w),
+                  loss.data_ptr(), _stream(a.device))
+        ctx.kind, ctx.entry = kind, entry
+        ctx.save_for_backward(a, b, w)
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        a, b = ctx.saved_tensors
+        a, b, w = ctx.saved_tensors
         g = g.contiguous()
         da = torch.empty_like(a)
-        rc = _lib.lib().dt_loss_bwd(ctx.kind, a.numel(), a.data_ptr(),
-                                    b.data_ptr() if b is not None else None, g.data_ptr(),
-                                    da.data_ptr(), torch.cuda.current_stream(a.device).cuda_stream)
-        if rc != 0:
-            raise _lib.DtError('dt_loss_bwd failed (%d)' % rc)
-        return da, None, None
+        _lib.call(ctx.entry + '_bwd', ctx.kind, a.numel(), a.data_ptr(), _ptr(b),
+                  *_w_arg(ctx.entry, w), g.data_ptr(), da.data_ptr(), _stream(a.device))
+        return da, None, None, None, None
+
+
+class _LossW(_Loss):
+    """_Loss as weighted_loss applies it: a grad_fn named after the dt_loss_w
+    pair, so a graph shows which kernels a loss ran on."""
 
 
 def _loss_applicable(*ts):
@@ -768,42 +699,8 @@ def _loss_applicable(*ts):
 def mse_loss(a, b):
     """F.mse_loss(a, b) (b without gradient) in one launch each way on the GPU."""
     if _loss_applicable(a, b) and not b.requires_grad:
-        return _Loss.apply(a, b.detach(), 0)
+        return _Loss.apply(a, b.detach(), None, 0, 'dt_loss')
     return F.mse_loss(a, b)
-
-
-class _LossW(torch.autograd.Function):
-    """dt_loss_w: mean(w * (a - b) ** 2) (kind 0) or mean(w * smooth_l1(a, b))
-    (kind 2), w the prioritized replay's importance weights (None: ones).  One
-    launch forward, one backward (gradient for `a` only: b is the detached
-    target, w the sampler's output)."""
-
-    @staticmethod
-    def forward(ctx, a, b, w, kind):
-        a, b = a.contiguous(), b.contiguous()
-        w = w.contiguous() if w is not None else None
-        loss = torch.empty((), device=a.device)
-        rc = _lib.lib().dt_loss_w(kind, a.numel(), a.data_ptr(), b.data_ptr(),
-                                  w.data_ptr() if w is not None else None, loss.data_ptr(),
-                                  torch.cuda.current_stream(a.device).cuda_stream)
-        if rc != 0:
-            raise _lib.DtError('dt_loss_w failed (%d)' % rc)
-        ctx.kind = kind
-        ctx.save_for_backward(a, b, w)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        a, b, w = ctx.saved_tensors
-        g = g.contiguous()
-        da = torch.empty_like(a)
-        rc = _lib.lib().dt_loss_w_bwd(ctx.kind, a.numel(), a.data_ptr(), b.data_ptr(),
-                                      w.data_ptr() if w is not None else None, g.data_ptr(),
-                                      da.data_ptr(),
-                                      torch.cuda.current_stream(a.device).cuda_stream)
-        if rc != 0:
-            raise _lib.DtError('dt_loss_w_bwd failed (%d)' % rc)
-        return da, None, None, None
 
 
 _LOSS_W_KINDS = {'mse_loss': 0, 'smooth_l1_loss': 2}
@@ -819,7 +716,7 @@ def weighted_loss(a, b, w, kind):
     ts = (a, b) if w is None else (a, b, w)
     if _loss_applicable(*ts) and not any(t.requires_grad for t in ts[1:]):
         return _LossW.apply(a, b.detach(), None if w is None else w.detach(),
-                            _LOSS_W_KINDS[kind])
+                            _LOSS_W_KINDS[kind], 'dt_loss_w')
     if kind == 'mse_loss':
         terms = (a - b) ** 2
     else:
@@ -830,5 +727,5 @@ def weighted_loss(a, b, w, kind):
 def neg_mean(a):
     """-1.0 * torch.mean(a) (the actor loss) in one launch each way on the GPU."""
     if _loss_applicable(a):
-        return _Loss.apply(a, None, 1)
+        return _Loss.apply(a, None, None, 1, 'dt_loss')
     return -1.0 * torch.mean(a)

@@ -140,6 +140,8 @@ class DDPGTrainer:
         self.split_target = False     # + the target critic trunk on a third (measured slower)
         self.fold_dropout = True      # dropouts folded into the linears after them (train_ops)
         self._pending_grads = {}      # module id -> its autograd gradients (_grads -> _opt_step)
+        self._drop = None             # the stages' ExitStack (_stages_scope) holding the drop pool
+        self.drop_sites_used = 0      # pool slices the last eager (or captured) stages took
         self.conv_search = bool(conv_search)
         self._graphs = None
         self._in = None
@@ -309,21 +311,25 @@ class DDPGTrainer:
 
     def _drop_open(self):
         """One launch draws every folded dropout's uniforms of the update
-        (instead of one dropout kernel a site); closed by _drop_close."""
+        (instead of one dropout kernel a site).  The pool lives on the stages'
+        ExitStack, so it closes when they end, however they end."""
         train_ops.FOLD_DROPOUT = self.fold_dropout
         k = self._drop_width() if (self.device.type == 'cuda' and self.dtype == torch.float32
                                    and self.fold_dropout) else None
         if k is None:
             return
-        self._drop_ctx = train_ops.drop_pool(self.DROP_SITES, self._in['obs'].shape[0], k,
-                                             self.device)
-        self._drop_buf = self._drop_ctx.__enter__()
+        self._drop_buf = self._drop.enter_context(train_ops.drop_pool(
+            self.DROP_SITES, self._in['obs'].shape[0], k, self.device))
+        # runs before the pool closes: how many slices the stages took
+        self._drop.callback(lambda: setattr(self, 'drop_sites_used', train_ops._DROP['next']))
 
-    def _drop_close(self):
-        ctx = getattr(self, '_drop_ctx', None)
-        if ctx is not None:
-            ctx.__exit__(None, None, None)
-            self._drop_ctx = None
+    @contextlib.contextmanager
+    def _stages_scope(self):
+        """Around one run of the stages (eager, or their capture): what
+        _stage_critic opens, the drop pool, cannot outlive it."""
+        self.drop_sites_used = 0
+        with contextlib.ExitStack() as self._drop:
+            yield
 
     def _stage_critic(self):
         x = self._in
@@ -425,7 +431,6 @@ class DDPGTrainer:
         # trainers.py:215-216, both pairs in one launch
         _SOFT.many([(self.target_actor, self.actor), (self.target_critic, self.critic)], self.tau)
         self._join(side, self._td)
-        self._drop_close()
         with torch.no_grad():
             self._metrics = (torch.sqrt(self._critic_loss), self._actor_loss)
 
@@ -433,12 +438,13 @@ class DDPGTrainer:
         stages = [self._stage_critic, self._stage_actor, self._stage_targets]
         groups = [stages] if self.sync_actor is None else [[st] for st in stages]
         self._graphs = []
-        for group in groups:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                for st in group:
-                    st()
-            self._graphs.append(g)
+        with self._stages_scope():
+            for group in groups:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    for st in group:
+                        st()
+                self._graphs.append(g)
         for opt in (self.actor_optim, self.critic_optim):
             if isinstance(opt, DeviceStep):
                 opt.finish_capture()
@@ -498,8 +504,9 @@ class DDPGTrainer:
                     if sync is not None:
                         sync()
         else:
-            for st, sync in zip((self._stage_critic, self._stage_actor, self._stage_targets),
-                                syncs):
-                st()
-                if sync is not None:
-                    sync()
+            with self._stages_scope():
+                for st, sync in zip((self._stage_critic, self._stage_actor, self._stage_targets),
+                                    syncs):
+                    st()
+                    if sync is not None:
+                        sync()

@@ -60,6 +60,32 @@ def test_library_loads_and_reports_abi(libpath):
     assert L.dt_abi_version() == _lib.ABI_VERSION
 
 
+def test_call_names_the_entry_point_that_failed():
+    """_lib.call: the arguments go through unchanged, 0 returns, any other
+    status raises DtError('<name> failed (<rc>)') -- on a stub library, so
+    without loading the real one."""
+    from aido1_amd import _lib
+
+    class Stub:
+        seen = []
+
+        def dt_stub(self, *args):
+            self.seen.append(args)
+            return 3
+
+        def dt_fine(self, *args):
+            self.seen.append(args)
+            return 0
+    stub = Stub()
+    with pytest.raises(_lib.DtError) as err:
+        _lib.call('dt_stub', 1, None, L=stub)
+    assert str(err.value) == 'dt_stub failed (3)'
+    assert _lib.call('dt_fine', 2, L=stub) is None
+    assert stub.seen == [(1, None), (2,)]
+    with pytest.raises(AttributeError):
+        _lib.call('dt_absent', L=stub)
+
+
 def test_no_gpu_fails_loudly():
     import torch
     if torch.cuda.is_available():

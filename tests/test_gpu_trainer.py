@@ -108,3 +108,88 @@ def test_two_stream_stages_equal_one_stream(gpu, graph):
             assert torch.equal(sa[k], sb[k]), k
     if graph:
         assert two._graphs is not None and one._graphs is not None
+
+
+# ---- the drop pool (train_ops.drop_pool) around the stages ---------------------------------
+def _keep_dropout(monkeypatch):
+    """make_trainer with config.json's dropouts left in (it zeroes them for
+    the golden runs, and with p = 0 no site folds and no pool is opened)."""
+    import test_trainer
+    monkeypatch.setattr(test_trainer, 'no_dropout', lambda net_config: net_config)
+
+
+@pytest.mark.parametrize('dropout', [False, True])
+def test_failed_update_releases_drop_pool(gpu, monkeypatch, dropout):
+    """An eager update that raises between _stage_critic (which opens the
+    pool) and the end of _stage_targets leaves no pool behind: _DROP is back
+    at its idle state, and three seeded updates of a trainer built afterwards
+    equal, bit for bit, those of one built after _DROP was reset by hand.
+    The failure is a host RuntimeError from a replaced _stage_actor."""
+    from aido1_amd import train_ops
+    torch.backends.cudnn.allow_tf32 = False
+    if dropout:
+        _keep_dropout(monkeypatch)
+    batch = formula_batch(16)
+    bad = make_trainer(gpu)
+
+    def fail():
+        raise RuntimeError('stage failed')
+    bad._stage_actor = fail
+    with pytest.raises(RuntimeError, match='stage failed'):
+        bad.update(batch)
+    assert train_ops._DROP['pool'] is None and train_ops._DROP['next'] == 0
+    # with dropouts the pool was open when the stage failed (the critic stage's sites)
+    assert (bad.drop_sites_used > 0) == dropout
+
+    def three_updates():
+        torch.manual_seed(7)
+        tr = make_trainer(gpu)
+        tds = [tr.update(batch)[1]['td_error'].clone() for _ in range(3)]
+        torch.cuda.synchronize()
+        return tr, tds
+    after, td_after = three_updates()
+    train_ops._DROP.update(pool=None, next=0)
+    control, td_control = three_updates()
+    for a, b in zip(td_after, td_control):
+        assert torch.equal(a, b)
+    for name in ('actor', 'critic', 'target_actor', 'target_critic'):
+        sa, sb = getattr(after, name).state_dict(), getattr(control, name).state_dict()
+        for k in sa:
+            assert torch.equal(sa[k], sb[k]), (name, k)
+
+
+@pytest.mark.parametrize('dropout', [False, True])
+@pytest.mark.parametrize('layout', ['default', 'split_target', 'importance_weights',
+                                    'one_stream'])
+def test_update_consumes_its_drop_sites(gpu, monkeypatch, layout, dropout):
+    """One eager update takes exactly DDPGTrainer.DROP_SITES slices of the
+    pool in every stage layout: none drawn past its end, none wasted.
+    make_trainer's own networks (dropout p = 0) fold nothing, so no pool is
+    opened and the count is 0."""
+    from aido1_amd import train_ops
+    if dropout:
+        _keep_dropout(monkeypatch)
+    tr = make_trainer(gpu, importance_weights=layout == 'importance_weights')
+    tr.split_target = layout == 'split_target'
+    tr.multi_stream = layout != 'one_stream'
+    tr.update(formula_batch(16))
+    torch.cuda.synchronize()
+    assert tr.drop_sites_used == (tr.DROP_SITES if dropout else 0)
+    assert train_ops._DROP['pool'] is None and train_ops._DROP['next'] == 0
+
+
+def test_no_pool_without_fold_dropout(gpu, monkeypatch):
+    """fold_dropout=False (the A/B switch): the dropouts stay torch's, no pool
+    is opened."""
+    from aido1_amd import train_ops
+    _keep_dropout(monkeypatch)
+    tr = make_trainer(gpu)
+    tr.fold_dropout = False
+    drawn = []
+    monkeypatch.setattr(train_ops, 'drop_pool', lambda *a, **k: drawn.append(a))
+    try:
+        tr.update(formula_batch(16))
+        torch.cuda.synchronize()
+    finally:
+        train_ops.FOLD_DROPOUT = True       # the global the trainer set (its default)
+    assert not drawn and tr.drop_sites_used == 0
