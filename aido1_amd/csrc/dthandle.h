@@ -22,7 +22,7 @@ struct dt_handle {
   void* map_buf = nullptr;
   dt::State st{};
   void* st_buf = nullptr;
-  size_t lds_bytes = 0;
+  size_t lds_bytes = 0;     // the map image the kernels stage (walker rows included)
   uint32_t env_base = 0;
   // observation path (dtrender.hip)
   dt_line_params line_params{};
@@ -40,6 +40,9 @@ struct dt_handle {
   // dt_render_objects: the footprint records the render draws (0: none)
   void* render_objs = nullptr;   // float [DT_MAX_RENDER_OBJECTS][DT_RENDER_OBJ_STRIDE]
   int32_t n_render_objs = 0;
+  // dt_render_walkers: a row per record above (0: none walk)
+  void* render_walk = nullptr;   // float [DT_MAX_RENDER_OBJECTS][DT_RENDER_WALK_STRIDE]
+  int32_t n_render_walk = 0;
   std::string err;
 };
 

@@ -338,6 +338,10 @@ struct RenderArgs {
   // e1.e1, e2.e2), the same for every decision of a group
   const float4* objs;
   int32_t n_objs;
+  // dt_render_walkers: a row per record (vel * hx, vel * hz, W, K; K = 0: the
+  // object is static), or null; the time is the env's Simulator step counter
+  const float4* walk;
+  const uint32_t* step_count;
 };
 
 // ---- fused render kernel ----------------------------------------------------------
@@ -356,7 +360,8 @@ struct RenderArgs {
 //       drawn with Bresenham, OR-ed in (raster byte encoding, dtrender.h):
 //       order-free, so one pass
 //   0c  (kObj: dt_render_objects) the map's object footprints: one object per
-//       lane projected and culled by its pixel box, the ones in view listed;
+//       lane (a walker's corner 0 moved to where the env's step counter puts
+//       it) projected and culled by its pixel box, the ones in view listed;
 //       then four lanes per (listed object, row of its box) test the row
 //       span's pixel centres against the rectangle and store PAL_RED over
 //       whatever lies below (a plain byte store: every object writes the
@@ -1299,9 +1304,12 @@ __device__ inline bool object_box(const View& V, float4 qa, float4 qb, uint2& bo
 // 0 <= d.e1 <= e1.e1 and 0 <= d.e2 <= e2.e2, in float32 without contraction
 // (tests/render_objects_ref.py restates it).  Ends with the barrier phase 1
 // needs.
-__device__ __forceinline__ void draw_objects(const RenderArgs& a, RenderLds& S, const View& V) {
+__device__ __forceinline__ void draw_objects(const RenderArgs& a, RenderLds& S, const View& V,
+                                             int e) {
   const int tid = opaque_tid();
   constexpr int T = kRenderThreads;
+  // dt_render_walkers (uniform branch): the env's time, as the decision left it
+  const uint32_t t = a.walk ? a.step_count[e] : 0u;
   for (int o0 = 0; o0 < a.n_objs; o0 += T) {
     const int o = o0 + tid;
     float4 qa, qb;
@@ -1310,6 +1318,19 @@ __device__ __forceinline__ void draw_objects(const RenderArgs& a, RenderLds& S, 
     if (o < a.n_objs) {
       qa = a.objs[2 * o];
       qb = a.objs[2 * o + 1];
+      if (a.walk) {
+        // walker_index (include/dtsim.h), then corner 0 moves idx steps; the
+        // edge vectors and squared lengths do not
+        const float4 w = a.walk[o];
+        const uint32_t W = (uint32_t)w.z, K = (uint32_t)w.w;
+        if (K != 0u) {
+          const uint32_t P = W + K, leg = t / P, p = t - leg * P;
+          const uint32_t m = p > W ? p - W : 0u;
+          const float idx = (float)((leg & 1u) ? K - m : m);
+          qa.x = qa.x + idx * w.x;
+          qa.y = qa.y + idx * w.y;
+        }
+      }
       vis = object_box(V, qa, qb, box);
     }
     const int slot = wave_slot1(&S.cnt[kNObj], vis);
@@ -1510,7 +1531,7 @@ __device__ __forceinline__ void render_env(const RenderArgs& a, RenderLds& S, in
     }
   }
   __syncthreads();
-  if (kObj) draw_objects(a, S, V);
+  if (kObj) draw_objects(a, S, V, e);
   RENT(6);
   RENDER_STOP(2);
 
@@ -2079,6 +2100,9 @@ void dt_render_free(dt_handle* h) {
   if (h->render_objs) (void)hipFree(h->render_objs);
   h->render_objs = nullptr;
   h->n_render_objs = 0;
+  if (h->render_walk) (void)hipFree(h->render_walk);
+  h->render_walk = nullptr;
+  h->n_render_walk = 0;
 }
 
 extern "C" {
@@ -2138,6 +2162,11 @@ static bool group_ok(const dt_render_io* a, const dt_render_io* b) {
 
 int dt_render2(dt_handle* h, const dt_render_io* io_a, const dt_render_io* io_b, void* stream) {
   if (!h || !io_a || !io_b) return DT_E_ARG;
+  if (h->n_render_walk > 0) {
+    h->err = "dt_render2: a handle with render walkers renders one decision a launch "
+             "(a pose snapshot carries no step counter)";
+    return DT_E_ARG;
+  }
   if (!group_ok(io_a, io_b)) {
     h->err = "dt_render2: two decisions of one ring: poses given, the same ring, "
              "different slots, separate masks, no rgb";
@@ -2149,6 +2178,11 @@ int dt_render2(dt_handle* h, const dt_render_io* io_a, const dt_render_io* io_b,
 int dt_render3(dt_handle* h, const dt_render_io* io_a, const dt_render_io* io_b,
                const dt_render_io* io_c, void* stream) {
   if (!h || !io_a || !io_b || !io_c) return DT_E_ARG;
+  if (h->n_render_walk > 0) {
+    h->err = "dt_render3: a handle with render walkers renders one decision a launch "
+             "(a pose snapshot carries no step counter)";
+    return DT_E_ARG;
+  }
   if (!group_ok(io_a, io_b) || !group_ok(io_a, io_c) || !group_ok(io_b, io_c)) {
     h->err = "dt_render3: three decisions of one ring: poses given, the same ring, "
              "different slots, separate masks, no rgb";
@@ -2247,6 +2281,8 @@ static int render_launch(dt_handle* h, const dt_render_io* io, const dt_render_i
   const bool big_r = a.line.dil_r >= 2;
   a.objs = (const float4*)h->render_objs;
   a.n_objs = h->n_render_objs;
+  a.walk = h->n_render_walk > 0 ? (const float4*)h->render_walk : nullptr;
+  a.step_count = h->st.step_count;
   decltype(&render_kernel<false, false, false>) kern;
   if (a.n_objs > 0)
     kern = a.index ? (big_r ? render_kernel<true, true, true> : render_kernel<true, false, true>)
@@ -2294,7 +2330,54 @@ int dt_render_objects(dt_handle* h, const float* recs, int32_t n) {
       HIP_OR_FAIL(h, hipMalloc(&h->render_objs, DT_MAX_RENDER_OBJECTS * rec));
     HIP_OR_FAIL(h, hipMemcpy(h->render_objs, recs, (size_t)n * rec, hipMemcpyHostToDevice));
   }
+  if (n != h->n_render_objs) h->n_render_walk = 0;   // the rows matched the old records
   h->n_render_objs = n;
+  return DT_OK;
+}
+
+int dt_render_walkers(dt_handle* h, const float* recs, int32_t n) {
+  if (!h) return DT_E_ARG;
+  if (n != 0 && n != h->n_render_objs) {
+    h->err = "dt_render_walkers: n must be 0 or the count dt_render_objects was given (" +
+             std::to_string(h->n_render_objs) + ")";
+    return DT_E_ARG;
+  }
+  if (n > 0 && !recs) {
+    h->err = "dt_render_walkers: recs is null";
+    return DT_E_ARG;
+  }
+  for (int o = 0; o < n; ++o) {
+    const float* r = recs + (size_t)o * DT_RENDER_WALK_STRIDE;
+    const std::string row = "dt_render_walkers: row " + std::to_string(o);
+    bool zero = true;
+    for (int i = 0; i < DT_RENDER_WALK_STRIDE; ++i) {
+      if (!isfinite(r[i])) {
+        h->err = row + " holds a non-finite value";
+        return DT_E_ARG;
+      }
+      zero = zero && r[i] == 0.0f;
+    }
+    if (zero) continue;   // a static object
+    const bool steps = r[2] >= 0.0f && r[2] < 16777216.0f && r[2] == floorf(r[2]) &&
+                       r[3] >= 0.0f && r[3] < 16777216.0f && r[3] == floorf(r[3]);
+    if (!steps) {
+      h->err = row + ": W and K must be whole numbers in [0, 2^24)";
+      return DT_E_ARG;
+    }
+    if (r[3] < 1.0f) {
+      h->err = row + ": K must be >= 1";
+      return DT_E_ARG;
+    }
+  }
+  DevGuard dg(h->device);
+  HIP_OR_FAIL(h, hipDeviceSynchronize());   // launches in flight read the rows
+  if (n > 0) {
+    const size_t rec = DT_RENDER_WALK_STRIDE * sizeof(float);
+    if (!h->render_walk)   // the largest size, once: a captured launch keeps a valid pointer
+      HIP_OR_FAIL(h, hipMalloc(&h->render_walk, DT_MAX_RENDER_OBJECTS * rec));
+    HIP_OR_FAIL(h, hipMemcpy(h->render_walk, recs, (size_t)n * rec, hipMemcpyHostToDevice));
+  }
+  h->n_render_walk = n;
   return DT_OK;
 }
 

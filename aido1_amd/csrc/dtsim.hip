@@ -249,6 +249,7 @@ struct Decision {
   double lp[4];
 };
 
+template <bool kWalk>
 __device__ __forceinline__ void sim_decision(const MapLds& M, const dt::Geo& g, const StepCfg& sc,
                                              bool active, float2 a, double& x, double& z,
                                              double& ang, double& c, double& s,
@@ -311,7 +312,8 @@ __device__ __forceinline__ void sim_decision(const MapLds& M, const dt::Geo& g, 
       // pose is valid.
       double lq[4] = {0.0, 0.0, 0.0, 0.0};
       const bool lq_inl = dt::lane_pos<false>(M, g, x, z, c, s, lq);
-      const bool vp = dt::valid_pose(M, g, x, z, c, s, 1.0);
+      // (kWalk: the walkers stand where the counter after its increments puts them)
+      const bool vp = dt::valid_pose<kWalk>(M, g, x, z, c, s, 1.0, step_count);
       if (rep == 1) STAMP(12);
       lp_fresh = false;
       double r;
@@ -326,7 +328,9 @@ __device__ __forceinline__ void sim_decision(const MapLds& M, const dt::Geo& g, 
         const double sp = sc.speed_measured ? speed : g.robot_speed;
         // compute_reward: proximity_penalty2 at the actual centre (0 without objects)
         const double pen =
-            M.n_obj ? dt::proximity_penalty(M, g, x + g.off * c, z + g.off * (-s)) : 0.0;
+            M.n_obj ? dt::proximity_penalty<kWalk>(M, g, x + g.off * c, z + g.off * (-s),
+                                                   step_count)
+                    : 0.0;
         lp_fresh = true;
         lp_inl = lq_inl;
         lp[0] = lq[0];
@@ -363,6 +367,8 @@ __device__ __forceinline__ void sim_decision(const MapLds& M, const dt::Geo& g, 
 // The pose, counters and spawn-ahead bookkeeping stay in registers across the
 // decisions and the map is staged once.  Outputs of decision d are at
 // [d * n + env].  Blocks past n_step_blocks are the spawn-ahead refill.
+// kWalk: the handle has walkers (dt_set_walkers); fixed for a launch, the host picks.
+template <bool kWalk>
 __global__ __launch_bounds__(kBlock) void step_kernel(dt::State st, dt::MapDev md, dt::Geo g,
                                                   StepCfg sc, int n, uint32_t env_base, int k,
                                                   const float2* __restrict__ act,
@@ -414,7 +420,7 @@ __global__ __launch_bounds__(kBlock) void step_kernel(dt::State st, dt::MapDev m
       words[q] = __hip_atomic_load(st.pre_key + (size_t)q * n + ei, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
   }
-  const MapLds M = dt::stage_map(md, lds);
+  const MapLds M = dt::stage_map<kWalk>(md, lds);
   STAMP(1);
   // bit i: key + i is ready (written by an earlier launch); of those, failed
   const uint32_t key0 = key;
@@ -449,7 +455,7 @@ __global__ __launch_bounds__(kBlock) void step_kernel(dt::State st, dt::MapDev m
     asm volatile("" ::: "memory");  // keep the loads here, ahead of the decision
 
     Decision D;
-    sim_decision(M, g, sc, active, a, x, z, ang, c, s, step_count, env_step, D);
+    sim_decision<kWalk>(M, g, sc, active, a, x, z, ang, c, s, step_count, env_step, D);
 
     // auto-reset (VectorEnv): a finished env takes the reset pose of its next
     // spawn key; a key not ready is computed here, the whole wave on one env
@@ -578,8 +584,11 @@ struct FanX {  // [parity][env][step], rows padded to 4 for wide LDS reads
 
 // kLean: the common configuration as compile-time facts (wheel-velocity
 // actions clipped to [-1, 1], the nominal speed in the reward, auto-reset, no
-// collidable objects); the generic instantiation reads them from StepCfg / the map
-template <bool kLean>
+// collidable objects); the generic instantiation reads them from StepCfg / the map.
+// kWalk (never with kLean): the handle has walkers; wave 0 tests the decision's
+// three poses against the walkers at step counts t + 1, t + 2, t + 3 (pose r is
+// used only if the steps before it were taken, so its counter is t + r).
+template <bool kLean, bool kWalk = false>
 __global__ __launch_bounds__(kFanBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) void step_fan_kernel(dt::State st, dt::MapDev md,
                                                              dt::Geo g, StepCfg sc, int n,
                                                              uint32_t env_base, int k,
@@ -647,7 +656,7 @@ __global__ __launch_bounds__(kFanBlock) __attribute__((amdgpu_waves_per_eu(2, 2)
         if (e0 + j < n) sslot[i] = st.pre[(size_t)row * n + e0 + j];
       }
   }
-  const MapLds M = dt::stage_map(md, lds);   // its barrier also covers sact
+  const MapLds M = dt::stage_map<kWalk>(md, lds);   // its barrier also covers sact
   const uint32_t key0 = key;
   uint32_t ready = 0u, failed = 0u;
   if (sc.auto_reset) {
@@ -753,9 +762,11 @@ __global__ __launch_bounds__(kFanBlock) __attribute__((amdgpu_waves_per_eu(2, 2)
     if (wave == 0) {
 #pragma unroll
       for (int r = 1; r <= kFanSteps; ++r) {
-        const bool vp = dt::valid_pose_q<!kLean>(M, g, q, px[r], pz[r], pc[r], ps[r], 1.0);
-        const double pen = objs ? dt::proximity_penalty(M, g, px[r] + g.off * pc[r],
-                                                        pz[r] + g.off * (-ps[r]))
+        const uint32_t tw = step_count + (uint32_t)r;
+        const bool vp =
+            dt::valid_pose_q<!kLean, kWalk>(M, g, q, px[r], pz[r], pc[r], ps[r], 1.0, tw);
+        const double pen = objs ? dt::proximity_penalty<kWalk>(M, g, px[r] + g.off * pc[r],
+                                                               pz[r] + g.off * (-ps[r]), tw)
                                 : 0.0;
         if (lead) {
           X.vp[par][le][r - 1] = vp ? 1 : 0;
@@ -1194,7 +1205,9 @@ int dt_create(const dt_config* cfg, const dt_map* map, uint64_t seed, int32_t n_
                ob = (size_t)NO * DT_OBJ_STRIDE * 8, spb = (size_t)NS * 4 * 8,
                sb16 = ((size_t)(T + 1) * 2 + 15) & ~15ul, kb = ((size_t)T + 15) & ~15ul,
                db = (drv.size() * 2 + 15) & ~15ul;
-  if (hipMalloc(&h->map_buf, cb + ob + spb + sb16 + kb + db) != hipSuccess)
+  // (behind the drivable list: room for dt_set_walkers' rows, dt::walk_rows)
+  const size_t wb = (size_t)NO * dt::kWalkRec * 8;
+  if (hipMalloc(&h->map_buf, cb + ob + spb + sb16 + kb + db + wb) != hipSuccess)
     return fail("hipMalloc(map)");
   char* mb = (char*)h->map_buf;
   char* m_cs = mb + cb + ob + spb;
@@ -1285,6 +1298,69 @@ static int refill_from_counters(dt_handle* h, int e0, int e1) {
   return DT_OK;
 }
 
+// A walker value that must be a whole number of steps in [0, 2^24).
+static bool walk_steps_ok(double v) { return v >= 0.0 && v < 16777216.0 && v == floor(v); }
+
+int dt_set_walkers(dt_handle* h, const double* recs, int32_t n) {
+  if (!h) return DT_E_ARG;
+  const int NO = h->map.n_obj;
+  if (n != 0 && n != NO) {
+    h->err = "dt_set_walkers: n must be 0 or the handle's n_objects (" + std::to_string(NO) + ")";
+    return DT_E_ARG;
+  }
+  if (n > 0 && !recs) {
+    h->err = "dt_set_walkers: recs is null";
+    return DT_E_ARG;
+  }
+  std::vector<double> rows((size_t)n * dt::kWalkRec, 0.0);
+  for (int o = 0; o < n; ++o) {
+    const double* r = recs + (size_t)o * DT_WALK_STRIDE;
+    const std::string row = "dt_set_walkers: row " + std::to_string(o);
+    bool zero = true;
+    for (int i = 0; i < DT_WALK_STRIDE; ++i) {
+      if (!isfinite(r[i])) {
+        h->err = row + " holds a non-finite value";
+        return DT_E_ARG;
+      }
+      zero = zero && r[i] == 0.0;
+    }
+    if (zero) continue;   // a static object
+    if (!(r[2] > 0.0)) {
+      h->err = row + ": vel must be > 0";
+      return DT_E_ARG;
+    }
+    if (!walk_steps_ok(r[3]) || !walk_steps_ok(r[4])) {
+      h->err = row + ": W and K must be whole numbers in [0, 2^24)";
+      return DT_E_ARG;
+    }
+    if (r[4] < 1.0) {
+      h->err = row + ": K must be >= 1";
+      return DT_E_ARG;
+    }
+    double* d = rows.data() + (size_t)o * dt::kWalkRec;
+    d[0] = r[0];
+    d[1] = r[1];
+    d[2] = r[2];
+    const uint64_t wk = (uint64_t)(uint32_t)r[3] | ((uint64_t)(uint32_t)r[4] << 32);
+    memcpy(d + 3, &wk, 8);
+  }
+  const size_t lds = dt::map_lds_bytes(h->map.n_tiles, h->map.n_drivable, h->map.n_curves, NO,
+                                       h->map.n_spawn_obj, n);
+  if (lds > dt::kMaxMapLdsBytes) {
+    h->err = "dt_set_walkers: map image over the LDS budget (" + std::to_string(lds) + " B)";
+    return DT_E_ARG;
+  }
+  HIP_OR_FAIL(h, hipSetDevice(h->device));
+  // launches in flight read the rows: wait for them (synchronous, as dt_seed)
+  HIP_OR_FAIL(h, hipDeviceSynchronize());
+  if (n > 0)   // into the room dt_create left in the map's allocation
+    HIP_OR_FAIL(h, hipMemcpy((void*)dt::walk_rows(h->map), rows.data(),
+                             rows.size() * sizeof(double), hipMemcpyHostToDevice));
+  h->map.n_walk = n;
+  h->lds_bytes = lds;
+  return DT_OK;
+}
+
 int dt_seed(dt_handle* h, const uint64_t* seeds, uint64_t base, uint32_t env_id_base) {
   if (!h) return DT_E_ARG;
   h->env_base = env_id_base;
@@ -1335,7 +1411,8 @@ int dt_step_masked(dt_handle* h, const uint8_t* mask, const float* actions, doub
   // the ones consumed last decision overlaps this decision's step
   const int gs = (h->n + kBlock - 1) / kBlock;
   const int grid = gs + (h->sc.auto_reset ? refill_grid(h->n, kRefillEnvs) : 0);
-  hipLaunchKernelGGL(step_kernel, dim3(grid), dim3(kBlock), h->lds_bytes, s, h->st, h->map,
+  hipLaunchKernelGGL(h->map.n_walk > 0 ? step_kernel<true> : step_kernel<false>, dim3(grid),
+                     dim3(kBlock), h->lds_bytes, s, h->st, h->map,
                      h->geo, h->sc, h->n, h->env_base, 1, (const float2*)actions, reward,
                      reward_mod, done, (float2*)obs, lanepos, tile, gs, h->sc.max_spawn_attempts,
                      mask);
@@ -1376,7 +1453,10 @@ int dt_step_many(dt_handle* h, int32_t k, const float* actions, double* reward,
     for (int d0 = 0; d0 < k; d0 += kFanMaxK) {
       const int kk = k - d0 < kFanMaxK ? k - d0 : kFanMaxK;
       const size_t o = (size_t)d0 * h->n;
-      hipLaunchKernelGGL(lean ? step_fan_kernel<true> : step_fan_kernel<false>, dim3(gs + rb),
+      hipLaunchKernelGGL(lean ? step_fan_kernel<true>
+                              : (h->map.n_walk > 0 ? step_fan_kernel<false, true>
+                                                   : step_fan_kernel<false>),
+                         dim3(gs + rb),
                          dim3(kFanBlock),
                          off + slots + (size_t)kk * kFanEnvs * sizeof(float2), s, h->st, h->map,
                          h->geo,
@@ -1395,7 +1475,8 @@ int dt_step_many(dt_handle* h, int32_t k, const float* actions, double* reward,
   for (int d0 = 0; d0 < k; d0 += pose ? 1 : k) {
     const int kk = pose ? 1 : k;
     const size_t o = (size_t)d0 * h->n;
-    hipLaunchKernelGGL(step_kernel, dim3(gs + rb), dim3(kBlock), h->lds_bytes, s, h->st,
+    hipLaunchKernelGGL(h->map.n_walk > 0 ? step_kernel<true> : step_kernel<false>,
+                       dim3(gs + rb), dim3(kBlock), h->lds_bytes, s, h->st,
                        h->map, h->geo, h->sc, h->n, h->env_base, kk,
                        (const float2*)actions + o, reward + o, reward_mod + o, done + o,
                        obs ? (float2*)obs + o : (float2*)nullptr, (double*)nullptr,

@@ -81,6 +81,9 @@ constexpr int kCurveRec = 16;
 // Map image in device memory; staged into LDS by each block.
 struct MapDev {
   int32_t width, height, n_tiles, n_drivable, n_curves, n_obj, n_spawn_obj;
+  // dt_set_walkers: 0 (every object static) or n_obj rows of kWalkRec doubles
+  // behind `drivable` (walk_rows)
+  int32_t n_walk;
   const double* curves;     // [C,kCurveRec] ground-plane curve records (CurveRec)
   const double* obj;        // [n_obj, DT_OBJ_STRIDE] collidable static objects
   const double* spawn_obj;  // [n_spawn_obj, 4] x, y, z, spawn radius
@@ -88,6 +91,17 @@ struct MapDev {
   const int8_t* kind;       // [T]
   const int16_t* drivable;  // [n_drivable] tile index of the k-th drivable tile (load order)
 };
+
+// A walker row as the kernels read it (dt_set_walkers packs it on the host):
+// hx, hz, vel, and the bits of W | K << 32 (both below 2^24; K = 0: a static
+// object).
+constexpr int kWalkRec = 4;
+// The rows lie in the map's device allocation behind the drivable list
+// (dt_create leaves room for n_obj of them).
+__host__ __device__ inline const double* walk_rows(const MapDev& m) {
+  return reinterpret_cast<const double*>(reinterpret_cast<const unsigned char*>(m.drivable) +
+                                         (((size_t)m.n_drivable * 2 + 15) & ~(size_t)15));
+}
 
 // LDS view of the map.
 struct MapLds {
@@ -101,20 +115,28 @@ struct MapLds {
   // (16-23), kind > 0 (bit 24)
   const uint32_t* tinfo;
   int32_t width, height, n_drivable, n_obj, n_spawn_obj;
+  const double* walk;   // [n_obj, kWalkRec]: only stage_map<true> sets it
 };
 
 __host__ __device__ inline size_t map_lds_bytes(int n_tiles, int n_drivable, int n_curves,
-                                                int n_obj = 0, int n_spawn_obj = 0) {
+                                                int n_obj = 0, int n_spawn_obj = 0,
+                                                int n_walk = 0) {
   size_t b = (size_t)n_curves * kCurveRec * sizeof(double);
   b += ((size_t)n_obj * DT_OBJ_STRIDE + (size_t)n_spawn_obj * 4) * sizeof(double);
   b += ((size_t)(n_tiles + 1) * 2 + 15) & ~(size_t)15;
   b += ((size_t)n_tiles + 15) & ~(size_t)15;
   b += ((size_t)n_drivable * 2 + 15) & ~(size_t)15;
   b += (size_t)n_tiles * 4;
+  // the walker rows lie behind everything else, so the image without them is
+  // a prefix of the image with them (stage_map<false> of a handle with walkers)
+  if (n_walk > 0) b = ((b + 7) & ~(size_t)7) + (size_t)n_walk * kWalkRec * sizeof(double);
   return b;
 }
 
 // Cooperative copy of the map into LDS; every thread of the block calls it.
+// kWalk: the walker rows too (the step kernels' walker instantiations; the
+// spawn code never reads them: a walker is at home at every reset).
+template <bool kWalk = false>
 __device__ inline MapLds stage_map(const MapDev& m, unsigned char* lds) {
   double* cv = reinterpret_cast<double*>(lds);
   double* ob = cv + (size_t)m.n_curves * kCurveRec;
@@ -135,8 +157,17 @@ __device__ inline MapLds stage_map(const MapDev& m, unsigned char* lds) {
     const uint32_t k0 = m.curve_start[i], k1 = m.curve_start[i + 1];
     ti[i] = k0 | ((k1 - k0) << 16) | (m.kind[i] > 0 ? (1u << 24) : 0u);
   }
+  double* wk = nullptr;
+  if (kWalk) {
+    wk = reinterpret_cast<double*>(
+        lds + ((map_lds_bytes(m.n_tiles, m.n_drivable, m.n_curves, m.n_obj, m.n_spawn_obj) + 7) &
+               ~(size_t)7));
+    const double* src = walk_rows(m);
+    for (int i = tid; i < m.n_walk * kWalkRec; i += nt) wk[i] = src[i];
+  }
   __syncthreads();
   MapLds r;
+  r.walk = wk;
   r.curves = cv;
   r.obj = ob;
   r.spawn_obj = so;
@@ -267,8 +298,29 @@ __device__ inline bool drivable_fast(const MapLds& M, const Geo& g, double x, do
 // vectors (upstream: generate_norm's eigenvectors of the box, the same axes)
 // and each object's two precomputed norms; boxes overlap on an axis when their
 // closed projection intervals meet, and collide when they overlap on all four.
+//
+// kWalk (dt_set_walkers, include/dtsim.h): at Simulator step count t a walker
+// row stands idx steps of vel along its heading from home.  walk_shift gives
+// the shift (false for a static row); collide and proximity_penalty translate
+// the row's corners / centre by it, one add each, and collide takes the row's
+// own projections from the translated corners instead of the record.
+__device__ inline bool walk_shift(const MapLds& M, int o, uint32_t t, double& dx, double& dz) {
+  const double* w = M.walk + (size_t)o * kWalkRec;
+  const uint64_t wk = (uint64_t)__double_as_longlong(w[3]);
+  const uint32_t W = (uint32_t)wk, K = (uint32_t)(wk >> 32);
+  if (K == 0u) return false;   // uniform: the row is the same for every lane
+  const uint32_t P = W + K, leg = t / P, p = t - leg * P;
+  const uint32_t m = p > W ? p - W : 0u;
+  const uint32_t idx = (leg & 1u) ? K - m : m;
+  const double sh = (double)idx * w[2];
+  dx = sh * w[0];
+  dz = sh * w[1];
+  return true;
+}
+
+template <bool kWalk = false>
 __device__ inline bool collide(const MapLds& M, const Geo& g, double px, double pz, double c,
-                               double s) {
+                               double s, uint32_t t = 0u) {
   if (M.n_obj == 0) return false;
   const double fx = c, fz = -s, rx = s, rz = c;   // get_dir_vec, get_right_vec
   const double hw = g.robot_width * 0.5, hl = g.robot_length * 0.5;
@@ -298,6 +350,45 @@ __device__ inline bool collide(const MapLds& M, const Geo& g, double px, double 
   for (int o = 0; o < M.n_obj; ++o) {
     const double* ob = M.obj + (size_t)o * DT_OBJ_STRIDE;
     bool sep = false;
+    double wdx = 0.0, wdz = 0.0;
+    if (kWalk && walk_shift(M, o, t, wdx, wdz)) {
+      double wx[4], wz[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        wx[k] = ob[DT_OBJ_CORNERS + 2 * k] + wdx;
+        wz[k] = ob[DT_OBJ_CORNERS + 2 * k + 1] + wdz;
+      }
+#pragma unroll
+      for (int a = 0; a < 2 && !sep; ++a) {   // the walker's corners on the agent's axes
+        const double nx = a == 0 ? fx : rx, nz = a == 0 ? fz : rz;
+        double lo = wx[0] * nx + wz[0] * nz, hi = lo;
+#pragma unroll
+        for (int k = 1; k < 4; ++k) {
+          const double p = wx[k] * nx + wz[k] * nz;
+          lo = p < lo ? p : lo;
+          hi = p > hi ? p : hi;
+        }
+        sep = amax[a] < lo || hi < amin[a];
+      }
+#pragma unroll
+      for (int a = 0; a < 2 && !sep; ++a) {   // both boxes on the walker's axes
+        const double nx = ob[DT_OBJ_NORMS + 2 * a], nz = ob[DT_OBJ_NORMS + 2 * a + 1];
+        double lo = ax[0] * nx + az[0] * nz, hi = lo;
+        double wlo = wx[0] * nx + wz[0] * nz, whi = wlo;
+#pragma unroll
+        for (int k = 1; k < 4; ++k) {
+          const double p = ax[k] * nx + az[k] * nz;
+          lo = p < lo ? p : lo;
+          hi = p > hi ? p : hi;
+          const double wp = wx[k] * nx + wz[k] * nz;
+          wlo = wp < wlo ? wp : wlo;
+          whi = wp > whi ? wp : whi;
+        }
+        sep = hi < wlo || whi < lo;
+      }
+      if (!sep) return true;
+      continue;
+    }
     // the object's corners on the agent's axes
 #pragma unroll
     for (int a = 0; a < 2 && !sep; ++a) {
@@ -332,12 +423,19 @@ __device__ inline bool collide(const MapLds& M, const Geo& g, double px, double 
 // proximity_penalty2 at the actual centre: the sum of the negative
 // (|c_o - p| - AGENT_SAFETY_RAD - r_o) over the collidable objects
 // (safety_circle_overlap; 0 when no safety circle meets the agent's)
-__device__ inline double proximity_penalty(const MapLds& M, const Geo& g, double px, double pz) {
+template <bool kWalk = false>
+__device__ inline double proximity_penalty(const MapLds& M, const Geo& g, double px, double pz,
+                                           uint32_t t = 0u) {
   double pen = 0.0;
   for (int o = 0; o < M.n_obj; ++o) {
     const double* ob = M.obj + (size_t)o * DT_OBJ_STRIDE;
-    const double dx = ob[DT_OBJ_CENTER] - px, dy = ob[DT_OBJ_CENTER + 1] - 0.0,
-                 dz = ob[DT_OBJ_CENTER + 2] - pz;
+    double ox = ob[DT_OBJ_CENTER], oz = ob[DT_OBJ_CENTER + 2];
+    double wdx = 0.0, wdz = 0.0;
+    if (kWalk && walk_shift(M, o, t, wdx, wdz)) {   // a walker's centre at time t
+      ox = ox + wdx;
+      oz = oz + wdz;
+    }
+    const double dx = ox - px, dy = ob[DT_OBJ_CENTER + 1] - 0.0, dz = oz - pz;
     const double d = sqrt((dx * dx + dy * dy) + dz * dz);
     const double sc = (d - g.agent_safety_rad) - ob[DT_OBJ_SAFETY_RAD];
     if (sc < 0.0) pen = pen + sc;
@@ -359,8 +457,9 @@ __device__ inline bool inconvenient_spawn(const MapLds& M, double x, double z) {
 // _valid_pose with precomputed (c, s) = (cos, sin)(angle) (A6): the centre and
 // both wheels and the front drivable (scaled by safety) and no collision (the
 // unscaled agent box)
+template <bool kWalk = false>
 __device__ inline bool valid_pose(const MapLds& M, const Geo& g, double x, double z, double c,
-                                  double s, double safety) {
+                                  double s, double safety, uint32_t t = 0u) {
   const double px = x + g.off * c;
   const double pz = z + g.off * (-s);
   const double kw = (safety * 0.5) * g.robot_width;
@@ -372,7 +471,7 @@ __device__ inline bool valid_pose(const MapLds& M, const Geo& g, double x, doubl
   const bool d2 = drivable(M, g, px + kw * s, pz + kw * c);
   const bool d3 = drivable(M, g, px + kf * c, pz + kf * (-s));
   const bool ok = d0 & d1 & d2 & d3;
-  return ok && !collide(M, g, px, pz, c, s);
+  return ok && !collide<kWalk>(M, g, px, pz, c, s, t);
 }
 
 // valid_pose without the collision test: the four drivable probes (fast form)
@@ -653,13 +752,14 @@ __device__ inline bool probe_q(const MapLds& M, const Geo& g, int q, double x, d
 
 // _valid_pose at one pose over a quad, identical to valid_pose (kObj false:
 // the caller guarantees a map without collidable objects)
-template <bool kObj = true>
+template <bool kObj = true, bool kWalk = false>
 __device__ inline bool valid_pose_q(const MapLds& M, const Geo& g, int q, double x, double z,
-                                    double c, double s, double safety) {
+                                    double c, double s, double safety, uint32_t t = 0u) {
   bool near = false;
   bool ok = qall(probe_q(M, g, q, x, z, c, s, safety, near));
-  if (__builtin_expect(qany(near), 0)) return valid_pose(M, g, x, z, c, s, safety);
-  if (kObj && M.n_obj && ok) ok = !collide(M, g, x + g.off * c, z + g.off * (-s), c, s);
+  if (__builtin_expect(qany(near), 0)) return valid_pose<kWalk>(M, g, x, z, c, s, safety, t);
+  if (kObj && M.n_obj && ok)
+    ok = !collide<kWalk>(M, g, x + g.off * c, z + g.off * (-s), c, s, t);
   return ok;
 }
 

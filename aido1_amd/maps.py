@@ -27,6 +27,16 @@ not a traffic light, and its box meets a drivable tile (_collidable_object);
 every object counts for _inconvenient_spawn.  The meshes are not in this
 container, so the per-kind boxes below are assumptions (override them per
 object with ``mesh_min`` / ``mesh_max``).
+
+Walkers (upstream DuckieObj, recalled; parity unpinned like the static objects):
+a ``duckie`` with ``static: false`` waits `wait` seconds, walks `vel` metres a
+Simulator step along its heading until it is past `walk_distance` + 0.25,
+turns round, waits, walks back, and so on.  Without domain randomisation that
+is a function of time alone, so here a walker's displacement is a closed form
+of the env's Simulator step counter (walker_index; include/dtsim.h
+dt_set_walkers restates it) and the walker is at home whenever the counter is
+0 -- upstream keeps its objects moving across resets; build-defined.  A walker
+is always collidable.  Any other kind with ``static: false`` is refused.
 """
 import math
 import os
@@ -39,6 +49,12 @@ MAP_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'maps')
 
 SAFETY_RAD_MULT = 1.8
 MIN_SPAWN_OBJ_DIST = 0.25
+DEFAULT_FRAMERATE = 30
+# upstream DuckieObj defaults: metres per Simulator step (not scaled by
+# delta_time), seconds, and the margin added to walk_distance
+WALKER_VEL = 0.02
+WALKER_WAIT = 8.0
+WALKER_EXTRA_DIST = 0.25
 # mesh bounding boxes (min, max) in mesh units, y up -- ASSUMED (the upstream
 # .obj meshes are absent); with `height` only their proportions matter
 MESH_EXTENTS = {
@@ -162,6 +178,16 @@ def find_candidate_tiles(corners, tile_size):
     return [(x, y) for x in range(mn[0], mx[0] + 1) for y in range(mn[1], mx[1] + 1)]
 
 
+def walker_index(t, W, K):
+    """Steps of `vel` a walker stands from home at Simulator step count t: it
+    waits W steps, walks K, waits W, walks K back, ... (period 2 (W + K)).
+    All integer."""
+    P = W + K
+    leg, p = divmod(int(t), P)
+    m = max(0, p - W)
+    return m if leg % 2 == 0 else K - m
+
+
 @dataclass
 class MapObject:
     kind: str
@@ -175,6 +201,23 @@ class MapObject:
     norms: np.ndarray          # [2, 2]
     safety_radius: float
     collidable: bool = False
+    # a walker (kind duckie, static false): metres per Simulator step, seconds,
+    # metres; W wait steps and K walk steps a leg (walker_index); 0 when static
+    vel: float = 0.0
+    wait: float = 0.0
+    walk_distance: float = 0.0
+    W: int = 0
+    K: int = 0
+
+    @property
+    def walker(self):
+        return not self.static
+
+    @property
+    def heading(self):
+        """(hx, hz) = get_dir_vec(radians(rotate))."""
+        a = math.radians(self.rotate)
+        return math.cos(a), -math.sin(a)
 
     @property
     def spawn_radius(self):
@@ -193,7 +236,8 @@ class MapObject:
         return r
 
 
-def parse_object(desc, tile_size):
+def _parse_geometry(desc, tile_size):
+    """The MapObject of a map entry at its (home) pose."""
     kind = desc['kind']
     pos = desc['pos']
     x, z = pos[0:2]
@@ -211,14 +255,47 @@ def parse_object(desc, tile_size):
         raise ValueError('cannot specify both height and scale')
     scale = desc['height'] / mx[1] if 'height' in desc else float(desc.get('scale', 1.0))
     static = bool(desc.get('static', True))
-    if not static:
-        raise NotImplementedError('dynamic (non-static) objects are not supported')
     rotate = float(desc.get('rotate', 0.0))
     corners = generate_corners(world, mn, mx, np.radians(rotate), scale)
     ext = np.max([np.abs(mn), np.abs(mx)], axis=0)
     safety = SAFETY_RAD_MULT * (np.hypot(ext[0], ext[2]) * scale)
     return MapObject(kind, world, rotate, scale, mn, mx, static, corners,
                      generate_norm(corners), float(safety))
+
+
+def parse_object(desc, tile_size):
+    """A static object.  (A map's dynamic entries go through parse_walker.)"""
+    if not bool(desc.get('static', True)):
+        raise NotImplementedError('dynamic (non-static) objects are not supported')
+    return _parse_geometry(desc, tile_size)
+
+
+def parse_walker(desc, tile_size, frame_rate=DEFAULT_FRAMERATE):
+    """A walker: `kind: duckie` with `static: false`.  Any other dynamic kind
+    (the duckiebot follows a lane and reacts to the agent: per-env state and a
+    kernel of its own) is refused."""
+    if bool(desc.get('static', True)) or desc['kind'] != 'duckie':
+        raise NotImplementedError('dynamic (non-static) objects of kind %r are not supported '
+                                  '(only the walking duckie is)' % desc['kind'])
+    obj = _parse_geometry(desc, tile_size)
+    obj.vel = float(desc.get('vel', WALKER_VEL))
+    obj.wait = float(desc.get('wait', WALKER_WAIT))
+    obj.walk_distance = float(desc.get('walk_distance', tile_size))
+    if not (obj.vel > 0.0 and math.isfinite(obj.vel)) or obj.wait < 0.0 or \
+            not math.isfinite(obj.wait) or not math.isfinite(obj.walk_distance):
+        raise ValueError('walker needs vel > 0, wait >= 0 and a finite walk_distance')
+    obj.W = int(round(obj.wait * frame_rate))
+    D = obj.walk_distance + WALKER_EXTRA_DIST
+    k = max(1, int(D / obj.vel) - 2) if D > 0.0 else 1
+    while not float(k) * obj.vel > D:   # the smallest k >= 1 with float64(k) * vel > D
+        k += 1
+    while k > 1 and float(k - 1) * obj.vel > D:
+        k -= 1
+    obj.K = k
+    if obj.W >= 1 << 24 or obj.K >= 1 << 24:
+        raise ValueError('walker wait / walk steps must stay below 2^24')
+    obj.collidable = True
+    return obj
 
 
 @dataclass
@@ -240,9 +317,35 @@ class TileMap:
 
     @property
     def object_table(self):
-        """[K, 20] float64 records of the collidable objects (dt_map.objects)."""
-        recs = [o.record() for o in (self.objects or []) if o.collidable]
+        """[K, 20] float64 records of the collidable objects (dt_map.objects):
+        the static ones in load order, then the walkers (at home) in load order."""
+        recs = [o.record() for o in self._collidables()]
         return np.array(recs, np.float64).reshape(-1, 20)
+
+    def _collidables(self):
+        objs = [o for o in (self.objects or []) if o.collidable]
+        return [o for o in objs if not o.walker] + [o for o in objs if o.walker]
+
+    @property
+    def has_walkers(self):
+        return any(o.walker for o in (self.objects or []))
+
+    @property
+    def walker_table(self):
+        """[K, 5] float64, a row per object_table row (dt_set_walkers): hx, hz,
+        vel, W, K; a static row is all zero."""
+        recs = [[*o.heading, o.vel, float(o.W), float(o.K)] if o.walker else [0.0] * 5
+                for o in self._collidables()]
+        return np.array(recs, np.float64).reshape(-1, 5)
+
+    @property
+    def render_walker_table(self):
+        """[M, 4] float32, a row per render_table row (dt_render_walkers):
+        float32(vel * hx), float32(vel * hz), W, K -- the products in float64,
+        rounded once; a static row is all zero."""
+        recs = [[o.vel * o.heading[0], o.vel * o.heading[1], float(o.W), float(o.K)]
+                if o.walker else [0.0] * 4 for o in (self.objects or [])]
+        return np.array(recs, np.float64).reshape(-1, 4).astype(np.float32)
 
     @property
     def spawn_table(self):
@@ -287,7 +390,7 @@ def tile_curves(kind, orient, i, j, tile_size):
     return pts
 
 
-def parse_rows(rows, name='custom', tile_size=0.61, objects=()):
+def parse_rows(rows, name='custom', tile_size=0.61, objects=(), frame_rate=DEFAULT_FRAMERATE):
     H, W = len(rows), len(rows[0])
     kind = np.full(H * W, TILE_EMPTY, np.int8)
     orient = np.zeros(H * W, np.int8)
@@ -326,9 +429,10 @@ def parse_rows(rows, name='custom', tile_size=0.61, objects=()):
         curves[a:b] = pts
         h = pts[:, -1, :] - pts[:, 0, :]          # closest_curve_point: one Frobenius norm
         headings[a:b] = h / np.linalg.norm(h).reshape(1, -1)
-    objs = [parse_object(d, tile_size) for d in objects]
+    objs = [parse_object(d, tile_size) if d.get('static', True)
+            else parse_walker(d, tile_size, frame_rate) for d in objects]
     for o in objs:   # _collidable_object: static, not a traffic light, meets a drivable tile
-        if o.kind == 'trafficlight':
+        if o.kind == 'trafficlight' or o.walker:   # (a walker: always collidable)
             continue
         for (ti, tj) in find_candidate_tiles(o.corners, tile_size):
             if 0 <= ti < W and 0 <= tj < H and kind[tj * W + ti] > 0 and sat_intersects(
@@ -340,7 +444,7 @@ def parse_rows(rows, name='custom', tile_size=0.61, objects=()):
                    [list(r) for r in rows], objs)
 
 
-def load_map(name_or_path, tile_size=0.61):
+def load_map(name_or_path, tile_size=0.61, frame_rate=DEFAULT_FRAMERATE):
     path = name_or_path
     if not os.path.exists(path):
         path = os.path.join(MAP_DIR, name_or_path + '.yaml')
@@ -350,7 +454,7 @@ def load_map(name_or_path, tile_size=0.61):
     if isinstance(objects, dict):   # newer map format: named objects
         objects = list(objects.values())
     name = os.path.splitext(os.path.basename(path))[0]
-    return parse_rows(doc['tiles'], name, tile_size, objects)
+    return parse_rows(doc['tiles'], name, tile_size, objects, frame_rate)
 
 
 def available_maps():

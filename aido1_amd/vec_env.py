@@ -53,11 +53,17 @@ class VecEnv:
       config: EnvConfig; defaults reproduce launch_env() + config.json's wrapper.
       env_id_base: global id of env 0 (multi-GPU sharding: rank * n_envs), so
         shards draw disjoint spawn streams.
-      draw_objects: draw the map's static objects into the observation
+      draw_objects: draw the map's objects into the observation
         (dt_render_objects: each object's footprint, filled red; build-defined,
         the upstream meshes are absent).  Off by default: the frame then shows
         tiles and lane markings only, as it always has.  No effect on a map
-        without objects.
+        without objects.  A map's walkers (maps.py: a duckie with `static:
+        false`) are drawn where each env's step counter puts them
+        (dt_render_walkers); such a handle renders one decision a launch
+        (render_group_into is refused).
+
+    A map with walkers always has them in collision and the reward
+    (dt_set_walkers), whatever draw_objects says.
     """
 
     def __init__(self, n_envs, map_name=None, seed=123, device=None, config=None,
@@ -69,7 +75,8 @@ class VecEnv:
             device = torch.cuda.current_device() if torch.cuda.is_available() else 0
         self.device = torch.device('cuda', device)
         self.n = int(n_envs)
-        self.map = load_map(self.config.map_name, self.config.road_tile_size)
+        self.map = load_map(self.config.map_name, self.config.road_tile_size,
+                            self.config.frame_rate)
         self.env_id_base = int(env_id_base)
         self._L = _lib.lib()
         cfg = self.config.to_c()
@@ -92,12 +99,21 @@ class VecEnv:
                                self.n, device, ctypes.byref(h))
         _lib.check(self._L, None, rc, 'dt_create')
         self._h = h
+        if self.map.has_walkers:
+            walk = np.ascontiguousarray(self.map.walker_table, np.float64)
+            rc = self._L.dt_set_walkers(self._h, walk.ctypes.data_as(ctypes.c_void_p), len(walk))
+            _lib.check(self._L, self._h, rc, 'dt_set_walkers')
         self.draw_objects = bool(draw_objects)
         table = np.ascontiguousarray(self.map.render_table, np.float32)
         if self.draw_objects and len(table):   # (a map without objects: nothing to draw)
             rc = self._L.dt_render_objects(self._h, table.ctypes.data_as(ctypes.c_void_p),
                                            len(table))
             _lib.check(self._L, self._h, rc, 'dt_render_objects')
+            if self.map.has_walkers:
+                walk = np.ascontiguousarray(self.map.render_walker_table, np.float32)
+                rc = self._L.dt_render_walkers(self._h, walk.ctypes.data_as(ctypes.c_void_p),
+                                               len(walk))
+                _lib.check(self._L, self._h, rc, 'dt_render_walkers')
         self.seed(seed)
         self.out = StepOutput(self.n, self.device)
         self._reset_obs = torch.zeros(self.n, 2, dtype=torch.float32, device=self.device)

@@ -17,7 +17,8 @@
  *     Pointers documented "host" are ordinary host memory.
  *   - All device work is enqueued on the given stream (hipStream_t passed as
  *     void*; NULL = the default stream).  Only dt_get_state / dt_set_state /
- *     dt_seed / dt_render_objects synchronise.
+ *     dt_seed / dt_render_objects / dt_set_walkers / dt_render_walkers
+ *     synchronise.
  *   - One handle per (process, GPU).  Calls on one handle are not thread-safe.
  */
 #ifndef AIDO1_AMD_DTSIM_H
@@ -60,7 +61,11 @@ extern "C" {
                             14: dttrain.h dt_adamw, dt_sgd (the reference's
                                 other two optimisers as device steps);
                                 dt_render_objects (additive: the map's objects
-                                drawn into the observation, off by default) */
+                                drawn into the observation, off by default);
+                                dt_set_walkers, dt_render_walkers (additive:
+                                walking duckies in collision, reward and the
+                                frame; dt_map and dt_render_io keep their
+                                layouts, a handle without them is unchanged) */
 
 /* error codes */
 #define DT_OK 0
@@ -347,6 +352,85 @@ int dt_render3(dt_handle* h, const dt_render_io* io_a, const dt_render_io* io_b,
 #define DT_RENDER_OBJ_STRIDE 8
 #define DT_MAX_RENDER_OBJECTS 256
 int dt_render_objects(dt_handle* h, const float* recs, int32_t n);
+
+/* ---- walkers: moving objects (upstream DuckieObj, the walking duckie) ------
+ * Recalled from upstream, gym-duckietown being absent: parity is unpinned, as
+ * for the static objects.  Upstream's DuckieObj.step without domain
+ * randomisation is deterministic: it waits, walks `vel` a Simulator step along
+ * its heading until it is past `walk_distance`, turns round, waits again, and
+ * so on.  So a walker's pose is a closed form of the env's Simulator step
+ * counter t (step_count: update_physics increments it, a reset zeroes it,
+ * dt_get_state / dt_set_state carry it) and needs no per-env object state.
+ * A walker is at home whenever step_count == 0.  This is build-defined:
+ * upstream keeps its objects moving across resets; here a reset pose is
+ * computed ahead of time and may depend only on (seed, env, episode), so the
+ * spawn path (_inconvenient_spawn, the reset's _valid_pose) sees the walkers
+ * at home and is unchanged.
+ *
+ * Map keys (aido1_amd/maps.py).  A walker is an object with `kind: duckie` and
+ * `static: false`; any other kind with `static: false` is refused.  Optional
+ * keys: `vel`, metres per Simulator step, default 0.02 (upstream adds
+ * heading * vel a step, not scaled by delta_time); `wait`, seconds, default
+ * 8.0; `walk_distance`, metres, default the tile size (upstream adds 0.25).
+ * Host-side values: a = radians(rotate); heading (hx, hz) = (cos a, -sin a),
+ * as get_dir_vec; W = round(wait * frame_rate) steps; D = walk_distance +
+ * 0.25; K = the smallest integer k >= 1 with float64(k) * vel > D.
+ *
+ * Displacement at time t, all integer up to idx (maps.walker_index):
+ *   P = W + K;  leg = t / P;  p = t % P;  m = max(0, p - W)
+ *   idx = m on an even leg, K - m on an odd leg
+ *   s = float64(idx) * vel;  (dx, dz) = (s * hx, s * hz)     no contraction
+ * What moves: the object's four corners and its centre are each translated by
+ * one float64 add (x + dx, z + dz).  Its two axes do not change.  Its own
+ * projections (DT_OBJ_PROJ) are recomputed from the translated corners: the
+ * min and max over the four corners of x * nx + z * nz (one rounding a
+ * product, one the sum; no contraction).  A static row keeps the projections
+ * of its record.  The wiggle angle is visual only and not modelled.
+ * Which t: _valid_pose and proximity_penalty2 after a physics update use the
+ * counter after its increment; the render uses the handle's step_count[e] as
+ * the decision left it (0 after an auto-reset: a respawned env's first frame
+ * shows the walkers at home).  A walker is always collidable, whether or not
+ * its home box meets a drivable tile.  In dt_map.objects the static
+ * collidables keep their load order and the walkers follow them in load
+ * order, so the penalty sum runs over statics first, then walkers. */
+
+/* Make rows of dt_map.objects walk.
+ *   recs  host [n, DT_WALK_STRIDE] f64, a row per dt_map.objects row: hx, hz,
+ *         vel, W, K (W and K integral, below 2^24); an all-zero row is a
+ *         static object
+ *   n     0 (off: every object static, as a new handle) or the handle's n_objects
+ * The walker rows are staged in LDS behind the map image, which grows by
+ * n * 32 bytes and must stay within the 48 KB dt_create allows.
+ * Synchronous (waits for the device, then uploads into a buffer the handle
+ * owns; nothing changes host-side per launch afterwards, so a captured graph
+ * keeps replaying correctly as long as n stays).  DT_E_ARG, with dt_last_error
+ * set and nothing changed, for: n neither 0 nor n_objects, recs NULL with
+ * n > 0, a non-finite value, vel <= 0 on a non-zero row, K < 1 on a non-zero
+ * row, a W or K that is negative, not integral or not below 2^24, or a map
+ * image over the LDS budget. */
+#define DT_WALK_STRIDE 5
+int dt_set_walkers(dt_handle* h, const double* recs, int32_t n);
+
+/* Make records of dt_render_objects walk in the frame.
+ *   recs  host [n, DT_RENDER_WALK_STRIDE] f32, a row per dt_render_objects
+ *         record: float32(vel * hx), float32(vel * hz) (the products in
+ *         float64, rounded once), W, K; an all-zero row is a static object
+ *   n     0 (off) or the count dt_render_objects was given last
+ * The render moves corner 0 of a walker's record before anything else reads
+ * it: q0 + float32(idx) * wx and q1 + float32(idx) * wz in float32, each
+ * operation rounded (no fused multiply-add), idx as above from the handle's
+ * step_count[e] -- also when dt_render_io.pose is set: the pose snapshot
+ * carries no time, the time is the handle's current step_count.  The edge
+ * vectors and squared lengths do not move.  dt_render2 / dt_render3 on a
+ * handle with render walkers uploaded return DT_E_ARG: a grouped launch
+ * renders several decisions from dt_step_many's pose output, which carries no
+ * step counter.  A later dt_render_objects with another count switches the
+ * walkers off (n = 0).  Synchronous.  DT_E_ARG, with dt_last_error set and
+ * nothing changed, for: n neither 0 nor that count, recs NULL with n > 0, a
+ * non-finite value, K < 1 on a non-zero row, a W or K that is negative, not
+ * integral or not below 2^24. */
+#define DT_RENDER_WALK_STRIDE 4
+int dt_render_walkers(dt_handle* h, const float* recs, int32_t n);
 
 /* Diagnostics of that dispatch order (synchronises): launches so far, each
  * env's last recorded cost (shader cycles) and the order the next launch

@@ -1,7 +1,10 @@
 """Decision throughput of dt_step_many for several k against HIP graphs of
 dt_step (config 2: 4096 envs, loop_empty, U[0,1)^2 actions).
 
-  python tools/step_many_probe.py [--decisions 480]
+  python tools/step_many_probe.py [--decisions 480] [--map NAME_OR_PATH] [--no-graph]
+
+--map: another map (a name in aido1_amd/maps or a map file), e.g.
+loop_pedestrians against its all-static twin: the walkers' cost in the step.
 """
 import argparse
 import json
@@ -16,6 +19,8 @@ def main():
     p = argparse.ArgumentParser()
     p.add_argument('--decisions', type=int, default=480)
     p.add_argument('--ks', default='1,4,8,16,30,60,120')
+    p.add_argument('--map', default='loop_empty')
+    p.add_argument('--no-graph', action='store_true', help='skip the dt_step graphs')
     args = p.parse_args()
     import torch
     from aido1_amd.config import EnvConfig
@@ -27,7 +32,7 @@ def main():
     acts = torch.rand(D + 30, n, 2, generator=g, device=dev)
     res = {}
     for k in [int(v) for v in args.ks.split(',')]:
-        env = VecEnv(n, seed=1234, device=0, config=EnvConfig(map_name='loop_empty'))
+        env = VecEnv(n, seed=1234, device=0, config=EnvConfig(map_name=args.map))
         env.reset()
         out = StepOutput(k * n, dev, lanepos=False, tile=False)
         for i in range(30):
@@ -45,7 +50,10 @@ def main():
                                    env_steps_per_s=st['sim_steps'] / dt,
                                    resets_per_decision=st['resets'] / max(1, st['decisions']) * n)
         env.close()
-    env = VecEnv(n, seed=1234, device=0, config=EnvConfig(map_name='loop_empty'))
+    if args.no_graph:
+        print(json.dumps(res, indent=1), flush=True)
+        return
+    env = VecEnv(n, seed=1234, device=0, config=EnvConfig(map_name=args.map))
     env.reset()
     out = StepOutput(n, dev, lanepos=False, tile=False)
     graphs = [env.capture(acts[30 + c * 30:30 + (c + 1) * 30], out) for c in range(D // 30)]
