@@ -185,6 +185,9 @@ def bind(L):
         'dt_render_objects': (ctypes.c_int, [vp, vp, i32]),
         'dt_set_walkers': (ctypes.c_int, [vp, vp, i32]),
         'dt_render_walkers': (ctypes.c_int, [vp, vp, i32]),
+        'dt_bot_path': (ctypes.c_int, [vp, vp, vp, i32, i32, vp]),
+        'dt_set_bots': (ctypes.c_int, [vp, vp, vp, i32, i32]),
+        'dt_render_bots': (ctypes.c_int, [vp, vp, vp, i32, i32]),
         'dt_copy_pose': (ctypes.c_int, [vp, vp, vp]),
         'dt_render_order': (ctypes.c_int, [vp, ctypes.POINTER(u32), vp, vp]),
         'dt_palette_gray': (ctypes.c_int, [ctypes.POINTER(ctypes.c_float)]),

@@ -2,6 +2,7 @@
 // (dtsim.hip) and observation (dtrender.hip) translation units.
 #pragma once
 #include <string>
+#include <vector>
 
 #include "dtrender.h"
 #include "dtsim_common.h"
@@ -43,6 +44,18 @@ struct dt_handle {
   // dt_render_walkers: a row per record above (0: none walk)
   void* render_walk = nullptr;   // float [DT_MAX_RENDER_OBJECTS][DT_RENDER_WALK_STRIDE]
   int32_t n_render_walk = 0;
+  std::vector<uint8_t> render_walker;   // [n_render_walk]: the record walks (K != 0)
+  // dt_set_walkers' packed rows (empty: none) and dt_set_bots' table: the two
+  // share the map's mover rows, which set_movers (dtsim.hip) composes
+  std::vector<double> walk_rows_host;   // [n_obj][dt::kWalkRec]
+  std::vector<int32_t> bot_row;         // [n_bots] rows of dt_map.objects
+  void* bot_tab = nullptr;              // double [bot_rows][n_bots][DT_OBJ_STRIDE]
+  int32_t bot_rows = 0;
+  // dt_render_bots: the frame's bot table and each bot's render record (0: none)
+  void* render_bot_tab = nullptr;       // float [rows][n][DT_RENDER_OBJ_STRIDE]
+  void* render_bot_col = nullptr;       // int32 [DT_MAX_RENDER_OBJECTS]: column or -1
+  int32_t n_render_bots = 0, render_bot_rows = 0;
+  std::vector<int32_t> render_bot_row;  // [n_render_bots] records of dt_render_objects
   std::string err;
 };
 

@@ -342,6 +342,11 @@ struct RenderArgs {
   // object is static), or null; the time is the env's Simulator step counter
   const float4* walk;
   const uint32_t* step_count;
+  // dt_render_bots (the kObj = 2 kernels): the table [bot_rows, n_bots] of
+  // two-float4 records and each record's column of it (-1: not a bot)
+  const float4* bots;
+  const int32_t* bot_col;
+  uint32_t bot_rows, n_bots;
 };
 
 // ---- fused render kernel ----------------------------------------------------------
@@ -361,7 +366,9 @@ struct RenderArgs {
 //       order-free, so one pass
 //   0c  (kObj: dt_render_objects) the map's object footprints: one object per
 //       lane (a walker's corner 0 moved to where the env's step counter puts
-//       it) projected and culled by its pixel box, the ones in view listed;
+//       it; kObj = 2: a bot's whole record taken from dt_render_bots' table
+//       at that counter) projected and culled by its pixel box, the ones in
+//       view listed;
 //       then four lanes per (listed object, row of its box) test the row
 //       span's pixel centres against the rectangle and store PAL_RED over
 //       whatever lies below (a plain byte store: every object writes the
@@ -1304,12 +1311,13 @@ __device__ inline bool object_box(const View& V, float4 qa, float4 qb, uint2& bo
 // 0 <= d.e1 <= e1.e1 and 0 <= d.e2 <= e2.e2, in float32 without contraction
 // (tests/render_objects_ref.py restates it).  Ends with the barrier phase 1
 // needs.
+template <bool kBot>
 __device__ __forceinline__ void draw_objects(const RenderArgs& a, RenderLds& S, const View& V,
                                              int e) {
   const int tid = opaque_tid();
   constexpr int T = kRenderThreads;
   // dt_render_walkers (uniform branch): the env's time, as the decision left it
-  const uint32_t t = a.walk ? a.step_count[e] : 0u;
+  const uint32_t t = (kBot || a.walk) ? a.step_count[e] : 0u;
   for (int o0 = 0; o0 < a.n_objs; o0 += T) {
     const int o = o0 + tid;
     float4 qa, qb;
@@ -1318,6 +1326,17 @@ __device__ __forceinline__ void draw_objects(const RenderArgs& a, RenderLds& S, 
     if (o < a.n_objs) {
       qa = a.objs[2 * o];
       qb = a.objs[2 * o + 1];
+      if (kBot) {
+        // dt_render_bots: the record of row min(t, rows - 1) (o < n_objs, the
+        // size of bot_col; the host checked every column against n_bots)
+        const int32_t b = a.bot_col[o];
+        if (b >= 0) {
+          const uint32_t tt = t < a.bot_rows - 1u ? t : a.bot_rows - 1u;
+          const float4* r = a.bots + ((size_t)tt * a.n_bots + (uint32_t)b) * 2;
+          qa = r[0];
+          qb = r[1];
+        }
+      }
       if (a.walk) {
         // walker_index (include/dtsim.h), then corner 0 moves idx steps; the
         // edge vectors and squared lengths do not
@@ -1371,7 +1390,7 @@ __device__ __forceinline__ void draw_objects(const RenderArgs& a, RenderLds& S, 
 }
 
 // One env of render_kernel.
-template <bool kIdx, bool kBigR, bool kObj>
+template <bool kIdx, bool kBigR, int kObj>
 __device__ __forceinline__ void render_env(const RenderArgs& a, RenderLds& S, int e, int half,
                                            int vi
 #ifdef DTSIM_EARLY_MARKS
@@ -1531,7 +1550,7 @@ __device__ __forceinline__ void render_env(const RenderArgs& a, RenderLds& S, in
     }
   }
   __syncthreads();
-  if (kObj) draw_objects(a, S, V, e);
+  if (kObj) draw_objects<kObj == 2>(a, S, V, e);
   RENT(6);
   RENDER_STOP(2);
 
@@ -1644,7 +1663,8 @@ __device__ __forceinline__ void render_env(const RenderArgs& a, RenderLds& S, in
 // kIdx: palette-byte frames (a.index) instead of grey floats; kBigR: a
 // dilation radius of 2-3; kObj: the object footprints are drawn (phase 0c).
 // All are fixed for a launch: the host picks.
-template <bool kIdx, bool kBigR, bool kObj>
+// (kObj = 2: with dt_render_bots' table.)
+template <bool kIdx, bool kBigR, int kObj>
 __global__ __launch_bounds__(kRenderThreads) __attribute__((amdgpu_waves_per_eu(DTSIM_RENDER_WPE))) void
 render_kernel(RenderArgs a) {
   __shared__ __attribute__((aligned(16))) RenderLds S;
@@ -2103,6 +2123,10 @@ void dt_render_free(dt_handle* h) {
   if (h->render_walk) (void)hipFree(h->render_walk);
   h->render_walk = nullptr;
   h->n_render_walk = 0;
+  if (h->render_bot_tab) (void)hipFree(h->render_bot_tab);
+  if (h->render_bot_col) (void)hipFree(h->render_bot_col);
+  h->render_bot_tab = h->render_bot_col = nullptr;
+  h->n_render_bots = 0;
 }
 
 extern "C" {
@@ -2162,8 +2186,8 @@ static bool group_ok(const dt_render_io* a, const dt_render_io* b) {
 
 int dt_render2(dt_handle* h, const dt_render_io* io_a, const dt_render_io* io_b, void* stream) {
   if (!h || !io_a || !io_b) return DT_E_ARG;
-  if (h->n_render_walk > 0) {
-    h->err = "dt_render2: a handle with render walkers renders one decision a launch "
+  if (h->n_render_walk > 0 || h->n_render_bots > 0) {
+    h->err = "dt_render2: a handle with render walkers or bots renders one decision a launch "
              "(a pose snapshot carries no step counter)";
     return DT_E_ARG;
   }
@@ -2178,8 +2202,8 @@ int dt_render2(dt_handle* h, const dt_render_io* io_a, const dt_render_io* io_b,
 int dt_render3(dt_handle* h, const dt_render_io* io_a, const dt_render_io* io_b,
                const dt_render_io* io_c, void* stream) {
   if (!h || !io_a || !io_b || !io_c) return DT_E_ARG;
-  if (h->n_render_walk > 0) {
-    h->err = "dt_render3: a handle with render walkers renders one decision a launch "
+  if (h->n_render_walk > 0 || h->n_render_bots > 0) {
+    h->err = "dt_render3: a handle with render walkers or bots renders one decision a launch "
              "(a pose snapshot carries no step counter)";
     return DT_E_ARG;
   }
@@ -2283,13 +2307,21 @@ static int render_launch(dt_handle* h, const dt_render_io* io, const dt_render_i
   a.n_objs = h->n_render_objs;
   a.walk = h->n_render_walk > 0 ? (const float4*)h->render_walk : nullptr;
   a.step_count = h->st.step_count;
-  decltype(&render_kernel<false, false, false>) kern;
-  if (a.n_objs > 0)
-    kern = a.index ? (big_r ? render_kernel<true, true, true> : render_kernel<true, false, true>)
-                   : (big_r ? render_kernel<false, true, true> : render_kernel<false, false, true>);
+  const bool bots = a.n_objs > 0 && h->n_render_bots > 0;
+  a.bots = bots ? (const float4*)h->render_bot_tab : nullptr;
+  a.bot_col = (const int32_t*)h->render_bot_col;
+  a.bot_rows = (uint32_t)h->render_bot_rows;
+  a.n_bots = (uint32_t)h->n_render_bots;
+  decltype(&render_kernel<false, false, 0>) kern;
+  if (bots)
+    kern = a.index ? (big_r ? render_kernel<true, true, 2> : render_kernel<true, false, 2>)
+                   : (big_r ? render_kernel<false, true, 2> : render_kernel<false, false, 2>);
+  else if (a.n_objs > 0)
+    kern = a.index ? (big_r ? render_kernel<true, true, 1> : render_kernel<true, false, 1>)
+                   : (big_r ? render_kernel<false, true, 1> : render_kernel<false, false, 1>);
   else
-    kern = a.index ? (big_r ? render_kernel<true, true, false> : render_kernel<true, false, false>)
-                   : (big_r ? render_kernel<false, true, false> : render_kernel<false, false, false>);
+    kern = a.index ? (big_r ? render_kernel<true, true, 0> : render_kernel<true, false, 0>)
+                   : (big_r ? render_kernel<false, true, 0> : render_kernel<false, false, 0>);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, a);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -2330,7 +2362,11 @@ int dt_render_objects(dt_handle* h, const float* recs, int32_t n) {
       HIP_OR_FAIL(h, hipMalloc(&h->render_objs, DT_MAX_RENDER_OBJECTS * rec));
     HIP_OR_FAIL(h, hipMemcpy(h->render_objs, recs, (size_t)n * rec, hipMemcpyHostToDevice));
   }
-  if (n != h->n_render_objs) h->n_render_walk = 0;   // the rows matched the old records
+  if (n != h->n_render_objs) {   // the rows matched the old records
+    h->n_render_walk = 0;
+    h->render_walker.clear();
+    h->n_render_bots = 0;
+  }
   h->n_render_objs = n;
   return DT_OK;
 }
@@ -2368,6 +2404,12 @@ int dt_render_walkers(dt_handle* h, const float* recs, int32_t n) {
       h->err = row + ": K must be >= 1";
       return DT_E_ARG;
     }
+    if (h->n_render_bots > 0)
+      for (int32_t br : h->render_bot_row)
+        if (br == o) {
+          h->err = row + " is a render bot's record (dt_render_bots)";
+          return DT_E_ARG;
+        }
   }
   DevGuard dg(h->device);
   HIP_OR_FAIL(h, hipDeviceSynchronize());   // launches in flight read the rows
@@ -2378,6 +2420,85 @@ int dt_render_walkers(dt_handle* h, const float* recs, int32_t n) {
     HIP_OR_FAIL(h, hipMemcpy(h->render_walk, recs, (size_t)n * rec, hipMemcpyHostToDevice));
   }
   h->n_render_walk = n;
+  h->render_walker.assign((size_t)n, 0);
+  for (int o = 0; o < n; ++o)
+    h->render_walker[o] = recs[(size_t)o * DT_RENDER_WALK_STRIDE + 3] != 0.0f;
+  return DT_OK;
+}
+
+int dt_render_bots(dt_handle* h, const float* recs, const int32_t* render_row, int32_t rows,
+                   int32_t n) {
+  if (!h) return DT_E_ARG;
+  const int NR = h->n_render_objs;
+  if (n < 0 || n > NR) {
+    h->err = "dt_render_bots: n must be in 0..the count dt_render_objects was given (" +
+             std::to_string(NR) + ")";
+    return DT_E_ARG;
+  }
+  if (n == 0) {
+    DevGuard dg(h->device);
+    HIP_OR_FAIL(h, hipDeviceSynchronize());
+    h->n_render_bots = 0;
+    return DT_OK;
+  }
+  if (!recs || !render_row) {
+    h->err = "dt_render_bots: recs and render_row are required";
+    return DT_E_ARG;
+  }
+  if (rows < 1 || rows > DT_MAX_BOT_ROWS) {
+    h->err = "dt_render_bots: rows must be in 1.." + std::to_string(DT_MAX_BOT_ROWS);
+    return DT_E_ARG;
+  }
+  const size_t bytes = (size_t)rows * n * DT_RENDER_OBJ_STRIDE * sizeof(float);
+  if (bytes > (size_t)DT_MAX_BOT_BYTES) {
+    h->err = "dt_render_bots: the table (" + std::to_string(bytes) + " B) is over " +
+             std::to_string(DT_MAX_BOT_BYTES) + " B";
+    return DT_E_ARG;
+  }
+  std::vector<int32_t> col(DT_MAX_RENDER_OBJECTS, -1);
+  for (int b = 0; b < n; ++b) {
+    const int32_t o = render_row[b];
+    const std::string bot = "dt_render_bots: bot " + std::to_string(b);
+    if (o < 0 || o >= NR) {
+      h->err = bot + ": record " + std::to_string(o) + " is outside dt_render_objects' count";
+      return DT_E_ARG;
+    }
+    if (col[o] >= 0) {
+      h->err = bot + ": record " + std::to_string(o) + " is named twice";
+      return DT_E_ARG;
+    }
+    if (h->n_render_walk > 0 && h->render_walker[o]) {
+      h->err = bot + ": record " + std::to_string(o) + " is a render walker's";
+      return DT_E_ARG;
+    }
+    col[o] = b;
+  }
+  const size_t cnt = (size_t)rows * n * DT_RENDER_OBJ_STRIDE;
+  for (size_t i = 0; i < cnt; ++i)
+    if (!isfinite(recs[i])) {
+      h->err = "dt_render_bots: row " + std::to_string(i / ((size_t)n * DT_RENDER_OBJ_STRIDE)) +
+               " holds a non-finite value";
+      return DT_E_ARG;
+    }
+  DevGuard dg(h->device);
+  void* tab = nullptr;
+  HIP_OR_FAIL(h, hipMalloc(&tab, bytes));
+  hipError_t e = hipMemcpy(tab, recs, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess && !h->render_bot_col)
+    e = hipMalloc(&h->render_bot_col, DT_MAX_RENDER_OBJECTS * sizeof(int32_t));
+  if (e == hipSuccess) e = hipDeviceSynchronize();   // launches in flight read the old table
+  if (e == hipSuccess)
+    e = hipMemcpy(h->render_bot_col, col.data(), col.size() * sizeof(int32_t),
+                  hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(tab);
+    HIP_OR_FAIL(h, e);
+  }
+  if (h->render_bot_tab) (void)hipFree(h->render_bot_tab);
+  h->render_bot_tab = tab;
+  h->render_bot_rows = rows;
+  h->n_render_bots = n;
+  h->render_bot_row.assign(render_row, render_row + n);
   return DT_OK;
 }
 

@@ -249,7 +249,7 @@ struct Decision {
   double lp[4];
 };
 
-template <bool kWalk>
+template <bool kWalk, bool kBot>
 __device__ __forceinline__ void sim_decision(const MapLds& M, const dt::Geo& g, const StepCfg& sc,
                                              bool active, float2 a, double& x, double& z,
                                              double& ang, double& c, double& s,
@@ -313,7 +313,7 @@ __device__ __forceinline__ void sim_decision(const MapLds& M, const dt::Geo& g, 
       double lq[4] = {0.0, 0.0, 0.0, 0.0};
       const bool lq_inl = dt::lane_pos<false>(M, g, x, z, c, s, lq);
       // (kWalk: the walkers stand where the counter after its increments puts them)
-      const bool vp = dt::valid_pose<kWalk>(M, g, x, z, c, s, 1.0, step_count);
+      const bool vp = dt::valid_pose<kWalk, kBot>(M, g, x, z, c, s, 1.0, step_count);
       if (rep == 1) STAMP(12);
       lp_fresh = false;
       double r;
@@ -328,8 +328,8 @@ __device__ __forceinline__ void sim_decision(const MapLds& M, const dt::Geo& g, 
         const double sp = sc.speed_measured ? speed : g.robot_speed;
         // compute_reward: proximity_penalty2 at the actual centre (0 without objects)
         const double pen =
-            M.n_obj ? dt::proximity_penalty<kWalk>(M, g, x + g.off * c, z + g.off * (-s),
-                                                   step_count)
+            M.n_obj ? dt::proximity_penalty<kWalk, kBot>(M, g, x + g.off * c,
+                                                         z + g.off * (-s), step_count)
                     : 0.0;
         lp_fresh = true;
         lp_inl = lq_inl;
@@ -367,8 +367,9 @@ __device__ __forceinline__ void sim_decision(const MapLds& M, const dt::Geo& g, 
 // The pose, counters and spawn-ahead bookkeeping stay in registers across the
 // decisions and the map is staged once.  Outputs of decision d are at
 // [d * n + env].  Blocks past n_step_blocks are the spawn-ahead refill.
-// kWalk: the handle has walkers (dt_set_walkers); fixed for a launch, the host picks.
-template <bool kWalk>
+// kWalk: the handle has walkers (dt_set_walkers); kBot (with kWalk): it has
+// bots (dt_set_bots), with or without walkers.  Fixed for a launch, the host picks.
+template <bool kWalk, bool kBot = false>
 __global__ __launch_bounds__(kBlock) void step_kernel(dt::State st, dt::MapDev md, dt::Geo g,
                                                   StepCfg sc, int n, uint32_t env_base, int k,
                                                   const float2* __restrict__ act,
@@ -420,7 +421,7 @@ __global__ __launch_bounds__(kBlock) void step_kernel(dt::State st, dt::MapDev m
       words[q] = __hip_atomic_load(st.pre_key + (size_t)q * n + ei, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
   }
-  const MapLds M = dt::stage_map<kWalk>(md, lds);
+  const MapLds M = dt::stage_map<kWalk, kBot>(md, lds);
   STAMP(1);
   // bit i: key + i is ready (written by an earlier launch); of those, failed
   const uint32_t key0 = key;
@@ -455,7 +456,7 @@ __global__ __launch_bounds__(kBlock) void step_kernel(dt::State st, dt::MapDev m
     asm volatile("" ::: "memory");  // keep the loads here, ahead of the decision
 
     Decision D;
-    sim_decision<kWalk>(M, g, sc, active, a, x, z, ang, c, s, step_count, env_step, D);
+    sim_decision<kWalk, kBot>(M, g, sc, active, a, x, z, ang, c, s, step_count, env_step, D);
 
     // auto-reset (VectorEnv): a finished env takes the reset pose of its next
     // spawn key; a key not ready is computed here, the whole wave on one env
@@ -588,7 +589,9 @@ struct FanX {  // [parity][env][step], rows padded to 4 for wide LDS reads
 // kWalk (never with kLean): the handle has walkers; wave 0 tests the decision's
 // three poses against the walkers at step counts t + 1, t + 2, t + 3 (pose r is
 // used only if the steps before it were taken, so its counter is t + r).
-template <bool kLean, bool kWalk = false>
+// kBot (with kWalk): the handle has bots; their records come from the path
+// table at the same counters.
+template <bool kLean, bool kWalk = false, bool kBot = false>
 __global__ __launch_bounds__(kFanBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) void step_fan_kernel(dt::State st, dt::MapDev md,
                                                              dt::Geo g, StepCfg sc, int n,
                                                              uint32_t env_base, int k,
@@ -656,7 +659,7 @@ __global__ __launch_bounds__(kFanBlock) __attribute__((amdgpu_waves_per_eu(2, 2)
         if (e0 + j < n) sslot[i] = st.pre[(size_t)row * n + e0 + j];
       }
   }
-  const MapLds M = dt::stage_map<kWalk>(md, lds);   // its barrier also covers sact
+  const MapLds M = dt::stage_map<kWalk, kBot>(md, lds);   // its barrier also covers sact
   const uint32_t key0 = key;
   uint32_t ready = 0u, failed = 0u;
   if (sc.auto_reset) {
@@ -764,9 +767,9 @@ __global__ __launch_bounds__(kFanBlock) __attribute__((amdgpu_waves_per_eu(2, 2)
       for (int r = 1; r <= kFanSteps; ++r) {
         const uint32_t tw = step_count + (uint32_t)r;
         const bool vp =
-            dt::valid_pose_q<!kLean, kWalk>(M, g, q, px[r], pz[r], pc[r], ps[r], 1.0, tw);
-        const double pen = objs ? dt::proximity_penalty<kWalk>(M, g, px[r] + g.off * pc[r],
-                                                               pz[r] + g.off * (-ps[r]), tw)
+            dt::valid_pose_q<!kLean, kWalk, kBot>(M, g, q, px[r], pz[r], pc[r], ps[r], 1.0, tw);
+        const double pen = objs ? dt::proximity_penalty<kWalk, kBot>(
+                                      M, g, px[r] + g.off * pc[r], pz[r] + g.off * (-ps[r]), tw)
                                 : 0.0;
         if (lead) {
           X.vp[par][le][r - 1] = vp ? 1 : 0;
@@ -1034,6 +1037,116 @@ __global__ __launch_bounds__(64) void lane_pos_kernel(dt::State st, dt::MapDev m
   if (tile_out) tile_out[e] = dt::tile_of(M, g, x, z);
 }
 
+// ---- lane-following bots (include/dtsim.h "bots") --------------------------------
+// closest_curve_point(pos, angle): the point and unit tangent of the tile's
+// closest curve, false off the drivable tiles.  closest_curve, bezier_closest
+// and bez_xz are get_lane_pos2's own; the tangent is lane_pose_at's.
+__device__ inline bool curve_point(const MapLds& M, const dt::Geo& g, double x, double z, double c,
+                                   double s, double& qx, double& qz, double& tx, double& tz) {
+  const double* cv = dt::closest_curve(M, g, x, z, c, s);
+  if (!cv) return false;
+  const double tm = dt::bezier_closest(cv, x, z);
+  dt::bez_xz(cv, tm, qx, qz);
+  const double u = 1.0 - tm;
+  const double a0 = 3.0 * (u * u), a1 = 6.0 * u * tm, a2 = 3.0 * (tm * tm);
+  tx = a0 * cv[8];
+  tz = a0 * cv[9];
+  tx = tx + a1 * cv[10];
+  tz = tz + a1 * cv[11];
+  tx = tx + a2 * cv[12];
+  tz = tz + a2 * cv[13];
+  const double nn = sqrt(tx * tx + tz * tz);
+  tx = tx / nn;
+  tz = tz / nn;
+  return true;
+}
+
+constexpr int kBotChunk = 8192;   // Simulator steps a bot_path_kernel launch computes
+// why a path stopped (status word 1)
+constexpr int kBotOffRoad = 1, kBotNoFollow = 2, kBotNonFinite = 3;
+
+// One block per bot, lane 0 computes (a serial float64 chain, run once per
+// handle): rows t0 + 1 .. t1 of path [rows, n, 3] (x, z, angle), row t the
+// input of row t + 1.  status [n, 2]: the first row that could not be computed
+// (-1: none) and why; a bot whose path has stopped is skipped.
+__global__ __launch_bounds__(64) void bot_path_kernel(dt::MapDev md, dt::Geo g,
+                                                      const double* __restrict__ params, int n,
+                                                      int t0, int t1, double* path,
+                                                      int32_t* status) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  const MapLds M = dt::stage_map(md, lds);
+  const int b = (int)blockIdx.x;
+  if (threadIdx.x != 0 || b >= n || status[2 * b] >= 0) return;
+  const double* p = params + (size_t)b * DT_BOT_STRIDE;
+  const double vel = p[0], follow = p[1], gain = p[2], trim = p[3], radius = p[4], kk = p[5],
+               limit = p[6];
+  const double* r0 = path + ((size_t)t0 * n + b) * 3;
+  double x = r0[0], z = r0[1], ang = r0[2];
+  for (int t = t0; t < t1; ++t) {
+    double s, c;
+    sincos(ang, &s, &c);
+    int why = 0;
+    double px, pz, tx, tz, cx = 0.0, cz = 0.0;
+    if (!curve_point(M, g, x, z, c, s, px, pz, tx, tz)) {
+      why = kBotOffRoad;
+    } else {
+      double L = follow, ux, uz;
+      bool found = false;
+      for (int i = 0; i < 1000 && !found; ++i) {
+        found = curve_point(M, g, px + tx * L, pz + tz * L, c, s, cx, cz, ux, uz);
+        if (!found) L = L * 0.5;
+      }
+      if (!found) why = kBotNoFollow;
+    }
+    if (!why) {
+      double vx = cx - x, vz = cz - z;
+      const double vn = sqrt((vx * vx + 0.0 * 0.0) + vz * vz);
+      vx = vx / vn;
+      vz = vz / vn;
+      const double steer = gain * (-((s * vx + 0.0 * 0.0) + c * vz));
+      // SteeringToWheelVelWrapper.action on (vel, steer)
+      const double kri = (gain + trim) / kk, kli = (gain - trim) / kk;
+      const double wr_ = (vel + 0.5 * steer * g.wheel_dist) / radius;
+      const double wl_ = (vel - 0.5 * steer * g.wheel_dist) / radius;
+      double ur = wr_ * kri, ul = wl_ * kli;
+      ur = ur < limit ? ur : limit;
+      ur = ur > -limit ? ur : -limit;
+      ul = ul < limit ? ul : limit;
+      ul = ul > -limit ? ul : -limit;
+      // _update_pos(pos, angle, wheel_dist, [ul, ur], delta_time)
+      if (ul == ur) {
+        const double k = g.dt * ul;
+        x = x + k * c;
+        z = z + k * (-s);
+      } else {
+        const double l = g.wheel_dist;
+        const double w = (ur - ul) / l;
+        const double ri = (l * (ul + ur)) / (2.0 * (ul - ur));
+        const double rot = w * g.dt;
+        double sr, cr;
+        sincos(rot, &sr, &cr);
+        const double ox = x + ri * s, oz = z + ri * c;
+        const double dx = x - ox, dz = z - oz;
+        const double ndx = dx * cr + dz * sr;
+        const double ndz = dz * cr - dx * sr;
+        x = ox + ndx;
+        z = oz + ndz;
+        ang = ang + rot;
+      }
+      if (!(isfinite(x) && isfinite(z) && isfinite(ang))) why = kBotNonFinite;
+    }
+    if (why) {
+      status[2 * b] = t + 1;
+      status[2 * b + 1] = why;
+      return;
+    }
+    double* o = path + ((size_t)(t + 1) * n + b) * 3;
+    o[0] = x;
+    o[1] = z;
+    o[2] = ang;
+  }
+}
+
 int grid_of(int n) { return (n + dt::kWave - 1) / dt::kWave; }
 int refill_grid(int n, int ne) { return (n + ne - 1) / ne; }
 
@@ -1205,8 +1318,9 @@ int dt_create(const dt_config* cfg, const dt_map* map, uint64_t seed, int32_t n_
                ob = (size_t)NO * DT_OBJ_STRIDE * 8, spb = (size_t)NS * 4 * 8,
                sb16 = ((size_t)(T + 1) * 2 + 15) & ~15ul, kb = ((size_t)T + 15) & ~15ul,
                db = (drv.size() * 2 + 15) & ~15ul;
-  // (behind the drivable list: room for dt_set_walkers' rows, dt::walk_rows)
-  const size_t wb = (size_t)NO * dt::kWalkRec * 8;
+  // (behind the drivable list: room for dt_set_walkers' rows and dt_set_bots'
+  // header, dt::walk_rows)
+  const size_t wb = ((size_t)NO * dt::kWalkRec + dt::kBotHdr) * 8;
   if (hipMalloc(&h->map_buf, cb + ob + spb + sb16 + kb + db + wb) != hipSuccess)
     return fail("hipMalloc(map)");
   char* mb = (char*)h->map_buf;
@@ -1275,6 +1389,7 @@ int dt_destroy(dt_handle* h) {
   if (!h) return DT_E_ARG;
   (void)hipSetDevice(h->device);
   dt_render_free(h);
+  if (h->bot_tab) (void)hipFree(h->bot_tab);
   if (h->map_buf) (void)hipFree(h->map_buf);
   if (h->st_buf) (void)hipFree(h->st_buf);
   delete h;
@@ -1296,6 +1411,51 @@ static int refill_from_counters(dt_handle* h, int e0, int e1) {
   HIP_OR_FAIL(h, hipGetLastError());
   HIP_OR_FAIL(h, hipDeviceSynchronize());
   return DT_OK;
+}
+
+// The map's mover rows (dt::walk_rows): dt_set_walkers' packed rows (`walk`,
+// empty: none) with dt_set_bots' rows marked, then the bot header.  Checks the
+// LDS budget first (DT_E_ARG, nothing changed), then waits for the device and
+// uploads -- also when both are switched off: a graph captured with movers on
+// keeps its MapDev (n_walk = n_obj) and goes on staging the rows and header,
+// so they are cleared (every row static, a zero header) before a caller
+// frees the table they named.  The callers keep their own host-side state.
+static int set_movers(dt_handle* h, const char* who, const std::vector<double>& walk,
+                      const std::vector<int32_t>& bot_row, const void* bot_tab, int32_t bot_rows) {
+  const int NO = h->map.n_obj;
+  const int n = (walk.empty() && bot_row.empty()) ? 0 : NO;
+  const size_t lds = dt::map_lds_bytes(h->map.n_tiles, h->map.n_drivable, h->map.n_curves, NO,
+                                       h->map.n_spawn_obj, n);
+  if (lds > dt::kMaxMapLdsBytes) {
+    h->err = std::string(who) + ": map image over the LDS budget (" + std::to_string(lds) + " B)";
+    return DT_E_ARG;
+  }
+  std::vector<double> img((size_t)NO * dt::kWalkRec + dt::kBotHdr, 0.0);
+  if (!walk.empty()) memcpy(img.data(), walk.data(), walk.size() * sizeof(double));
+  for (size_t b = 0; b < bot_row.size(); ++b) {
+    const uint64_t wk = dt::kBotMark | (uint64_t)b;
+    memcpy(img.data() + (size_t)bot_row[b] * dt::kWalkRec + 3, &wk, 8);
+  }
+  const uint64_t hdr[2] = {bot_row.empty() ? 0ull : (uint64_t)(uintptr_t)bot_tab,
+                           bot_row.empty() ? 0ull
+                                           : (uint64_t)(uint32_t)bot_rows |
+                                                 ((uint64_t)bot_row.size() << 32)};
+  memcpy(img.data() + (size_t)NO * dt::kWalkRec, hdr, 16);
+  HIP_OR_FAIL(h, hipSetDevice(h->device));
+  // launches in flight read the rows: wait for them (synchronous, as dt_seed)
+  HIP_OR_FAIL(h, hipDeviceSynchronize());
+  if (NO > 0)   // into the room dt_create left in the map's allocation
+    HIP_OR_FAIL(h, hipMemcpy((void*)dt::walk_rows(h->map), img.data(),
+                             img.size() * sizeof(double), hipMemcpyHostToDevice));
+  h->map.n_walk = n;
+  h->lds_bytes = lds;
+  return DT_OK;
+}
+
+// step_kernel's instantiation for the handle's movers (fixed between uploads).
+static decltype(&step_kernel<false>) step_kernel_of(const dt_handle* h) {
+  if (!h->bot_row.empty()) return step_kernel<true, true>;
+  return h->map.n_walk > 0 ? step_kernel<true> : step_kernel<false>;
 }
 
 // A walker value that must be a whole number of steps in [0, 2^24).
@@ -1343,21 +1503,167 @@ int dt_set_walkers(dt_handle* h, const double* recs, int32_t n) {
     d[2] = r[2];
     const uint64_t wk = (uint64_t)(uint32_t)r[3] | ((uint64_t)(uint32_t)r[4] << 32);
     memcpy(d + 3, &wk, 8);
+    for (int32_t br : h->bot_row)
+      if (br == o) {
+        h->err = row + " is a bot's row (dt_set_bots)";
+        return DT_E_ARG;
+      }
   }
-  const size_t lds = dt::map_lds_bytes(h->map.n_tiles, h->map.n_drivable, h->map.n_curves, NO,
-                                       h->map.n_spawn_obj, n);
-  if (lds > dt::kMaxMapLdsBytes) {
-    h->err = "dt_set_walkers: map image over the LDS budget (" + std::to_string(lds) + " B)";
+  const int rc = set_movers(h, "dt_set_walkers", rows, h->bot_row, h->bot_tab, h->bot_rows);
+  if (rc != DT_OK) return rc;
+  h->walk_rows_host = rows;
+  return DT_OK;
+}
+
+int dt_bot_path(dt_handle* h, const double* home, const double* params, int32_t n, int32_t rows,
+                double* path_host) {
+  if (!h) return DT_E_ARG;
+  if (n < 1 || n > DT_MAX_RENDER_OBJECTS || rows < 1 || rows > DT_MAX_BOT_ROWS) {
+    h->err = "dt_bot_path: n must be in 1.." + std::to_string(DT_MAX_RENDER_OBJECTS) +
+             " and rows in 1.." + std::to_string(DT_MAX_BOT_ROWS);
     return DT_E_ARG;
   }
-  HIP_OR_FAIL(h, hipSetDevice(h->device));
-  // launches in flight read the rows: wait for them (synchronous, as dt_seed)
-  HIP_OR_FAIL(h, hipDeviceSynchronize());
-  if (n > 0)   // into the room dt_create left in the map's allocation
-    HIP_OR_FAIL(h, hipMemcpy((void*)dt::walk_rows(h->map), rows.data(),
-                             rows.size() * sizeof(double), hipMemcpyHostToDevice));
-  h->map.n_walk = n;
-  h->lds_bytes = lds;
+  if ((size_t)rows * n * 3 * sizeof(double) > (size_t)DT_MAX_BOT_BYTES) {
+    h->err = "dt_bot_path: the path (" + std::to_string((size_t)rows * n * 24) + " B) is over " +
+             std::to_string(DT_MAX_BOT_BYTES) + " B";
+    return DT_E_ARG;
+  }
+  if (!home || !params || !path_host) {
+    h->err = "dt_bot_path: home, params and path_host are required";
+    return DT_E_ARG;
+  }
+  for (int b = 0; b < n; ++b) {
+    const double* p = params + (size_t)b * DT_BOT_STRIDE;
+    const std::string bot = "dt_bot_path: bot " + std::to_string(b);
+    bool fin = isfinite(home[3 * b]) && isfinite(home[3 * b + 1]) && isfinite(home[3 * b + 2]);
+    for (int i = 0; i < DT_BOT_STRIDE; ++i) fin = fin && isfinite(p[i]);
+    if (!fin) {
+      h->err = bot + " holds a non-finite value";
+      return DT_E_ARG;
+    }
+    if (!(p[0] >= 0.0) || !(p[1] > 0.0) || !(p[4] > 0.0) || !(p[5] > 0.0) || !(p[6] >= 0.0)) {
+      h->err = bot + ": needs velocity >= 0, follow_dist > 0, radius > 0, k > 0, limit >= 0";
+      return DT_E_ARG;
+    }
+  }
+  DevGuard dg(h->device);
+  const size_t pb = (size_t)rows * n * 3 * sizeof(double), qb = (size_t)n * DT_BOT_STRIDE * 8,
+               sb = (size_t)n * 2 * sizeof(int32_t);
+  char* buf = nullptr;   // path | params | status
+  HIP_OR_FAIL(h, hipMalloc((void**)&buf, pb + qb + sb));
+  double* d_path = (double*)buf;
+  double* d_par = (double*)(buf + pb);
+  int32_t* d_st = (int32_t*)(buf + pb + qb);
+  std::vector<int32_t> st((size_t)n * 2, -1);
+  hipError_t e = hipMemcpy(d_path, home, (size_t)n * 3 * sizeof(double), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_par, params, qb, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(d_st, 0xFF, sb);
+  // without walkers' rows: the image every reset path stages
+  const size_t lds = dt::map_lds_bytes(h->map.n_tiles, h->map.n_drivable, h->map.n_curves,
+                                       h->map.n_obj, h->map.n_spawn_obj);
+  for (int t0 = 0; e == hipSuccess && t0 < rows - 1; t0 += kBotChunk) {
+    const int t1 = t0 + kBotChunk < rows - 1 ? t0 + kBotChunk : rows - 1;
+    hipLaunchKernelGGL(bot_path_kernel, dim3(n), dim3(64), lds, (hipStream_t)0, h->map, h->geo,
+                       d_par, n, t0, t1, d_path, d_st);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+  }
+  if (e == hipSuccess) e = hipMemcpy(st.data(), d_st, sb, hipMemcpyDeviceToHost);
+  int rc = DT_OK;
+  if (e != hipSuccess) {
+    h->err = std::string("dt_bot_path: ") + hipGetErrorString(e);
+    rc = DT_E_HIP;
+  }
+  for (int b = 0; rc == DT_OK && b < n; ++b)
+    if (st[2 * b] >= 0) {
+      static const char* why[] = {"", "it left the drivable tiles", "no follow point on a curve",
+                                  "a non-finite value"};
+      const int w = st[2 * b + 1] >= 1 && st[2 * b + 1] <= 3 ? st[2 * b + 1] : 0;
+      h->err = "dt_bot_path: bot " + std::to_string(b) + ", step " + std::to_string(st[2 * b]) +
+               ": the path is undefined (" + why[w] + ")";
+      rc = DT_E_ARG;
+    }
+  if (rc == DT_OK && hipMemcpy(path_host, d_path, pb, hipMemcpyDeviceToHost) != hipSuccess) {
+    h->err = "dt_bot_path: hipMemcpy(path) failed";
+    rc = DT_E_HIP;
+  }
+  (void)hipFree(buf);
+  return rc;
+}
+
+int dt_set_bots(dt_handle* h, const double* recs, const int32_t* object_row, int32_t rows,
+                int32_t n) {
+  if (!h) return DT_E_ARG;
+  const int NO = h->map.n_obj;
+  if (n < 0 || n > NO) {
+    h->err = "dt_set_bots: n must be in 0..n_objects (" + std::to_string(NO) + ")";
+    return DT_E_ARG;
+  }
+  std::vector<int32_t> bot_row;
+  void* tab = nullptr;
+  if (n > 0) {
+    if (!recs || !object_row) {
+      h->err = "dt_set_bots: recs and object_row are required";
+      return DT_E_ARG;
+    }
+    if (rows < 1 || rows > DT_MAX_BOT_ROWS) {
+      h->err = "dt_set_bots: rows must be in 1.." + std::to_string(DT_MAX_BOT_ROWS);
+      return DT_E_ARG;
+    }
+    const size_t bytes = (size_t)rows * n * DT_OBJ_STRIDE * sizeof(double);
+    if (bytes > (size_t)DT_MAX_BOT_BYTES) {
+      h->err = "dt_set_bots: the table (" + std::to_string(bytes) + " B) is over " +
+               std::to_string(DT_MAX_BOT_BYTES) + " B";
+      return DT_E_ARG;
+    }
+    for (int b = 0; b < n; ++b) {
+      const int32_t o = object_row[b];
+      const std::string bot = "dt_set_bots: bot " + std::to_string(b);
+      if (o < 0 || o >= NO) {
+        h->err = bot + ": row " + std::to_string(o) + " is outside n_objects";
+        return DT_E_ARG;
+      }
+      for (int c = 0; c < b; ++c)
+        if (object_row[c] == o) {
+          h->err = bot + ": row " + std::to_string(o) + " is named twice";
+          return DT_E_ARG;
+        }
+      if (!h->walk_rows_host.empty()) {
+        uint64_t wk;
+        memcpy(&wk, h->walk_rows_host.data() + (size_t)o * dt::kWalkRec + 3, 8);
+        if ((uint32_t)(wk >> 32) != 0u) {
+          h->err = bot + ": row " + std::to_string(o) + " is a walker's row (dt_set_walkers)";
+          return DT_E_ARG;
+        }
+      }
+    }
+    const size_t cnt = (size_t)rows * n * DT_OBJ_STRIDE;
+    for (size_t i = 0; i < cnt; ++i)
+      if (!isfinite(recs[i])) {
+        h->err = "dt_set_bots: row " + std::to_string(i / ((size_t)n * DT_OBJ_STRIDE)) +
+                 " holds a non-finite value";
+        return DT_E_ARG;
+      }
+    bot_row.assign(object_row, object_row + n);
+    DevGuard dg(h->device);
+    HIP_OR_FAIL(h, hipMalloc(&tab, bytes));
+    const hipError_t e = hipMemcpy(tab, recs, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)hipFree(tab);
+      HIP_OR_FAIL(h, e);
+    }
+  }
+  // (the kernels read the table's address from the header set_movers uploads,
+  // not from a launch argument: a captured graph follows a new table)
+  const int rc = set_movers(h, "dt_set_bots", h->walk_rows_host, bot_row, tab, rows);
+  if (rc != DT_OK) {
+    if (tab) (void)hipFree(tab);
+    return rc;
+  }
+  if (h->bot_tab) (void)hipFree(h->bot_tab);   // set_movers waited for the device
+  h->bot_tab = tab;
+  h->bot_rows = n > 0 ? rows : 0;
+  h->bot_row = bot_row;
   return DT_OK;
 }
 
@@ -1411,8 +1717,7 @@ int dt_step_masked(dt_handle* h, const uint8_t* mask, const float* actions, doub
   // the ones consumed last decision overlaps this decision's step
   const int gs = (h->n + kBlock - 1) / kBlock;
   const int grid = gs + (h->sc.auto_reset ? refill_grid(h->n, kRefillEnvs) : 0);
-  hipLaunchKernelGGL(h->map.n_walk > 0 ? step_kernel<true> : step_kernel<false>, dim3(grid),
-                     dim3(kBlock), h->lds_bytes, s, h->st, h->map,
+  hipLaunchKernelGGL(step_kernel_of(h), dim3(grid), dim3(kBlock), h->lds_bytes, s, h->st, h->map,
                      h->geo, h->sc, h->n, h->env_base, 1, (const float2*)actions, reward,
                      reward_mod, done, (float2*)obs, lanepos, tile, gs, h->sc.max_spawn_attempts,
                      mask);
@@ -1454,8 +1759,10 @@ int dt_step_many(dt_handle* h, int32_t k, const float* actions, double* reward,
       const int kk = k - d0 < kFanMaxK ? k - d0 : kFanMaxK;
       const size_t o = (size_t)d0 * h->n;
       hipLaunchKernelGGL(lean ? step_fan_kernel<true>
-                              : (h->map.n_walk > 0 ? step_fan_kernel<false, true>
-                                                   : step_fan_kernel<false>),
+                              : (!h->bot_row.empty()
+                                     ? step_fan_kernel<false, true, true>
+                                     : (h->map.n_walk > 0 ? step_fan_kernel<false, true>
+                                                          : step_fan_kernel<false>)),
                          dim3(gs + rb),
                          dim3(kFanBlock),
                          off + slots + (size_t)kk * kFanEnvs * sizeof(float2), s, h->st, h->map,
@@ -1475,8 +1782,7 @@ int dt_step_many(dt_handle* h, int32_t k, const float* actions, double* reward,
   for (int d0 = 0; d0 < k; d0 += pose ? 1 : k) {
     const int kk = pose ? 1 : k;
     const size_t o = (size_t)d0 * h->n;
-    hipLaunchKernelGGL(h->map.n_walk > 0 ? step_kernel<true> : step_kernel<false>,
-                       dim3(gs + rb), dim3(kBlock), h->lds_bytes, s, h->st,
+    hipLaunchKernelGGL(step_kernel_of(h), dim3(gs + rb), dim3(kBlock), h->lds_bytes, s, h->st,
                        h->map, h->geo, h->sc, h->n, h->env_base, kk,
                        (const float2*)actions + o, reward + o, reward_mod + o, done + o,
                        obs ? (float2*)obs + o : (float2*)nullptr, (double*)nullptr,

@@ -81,8 +81,8 @@ constexpr int kCurveRec = 16;
 // Map image in device memory; staged into LDS by each block.
 struct MapDev {
   int32_t width, height, n_tiles, n_drivable, n_curves, n_obj, n_spawn_obj;
-  // dt_set_walkers: 0 (every object static) or n_obj rows of kWalkRec doubles
-  // behind `drivable` (walk_rows)
+  // dt_set_walkers / dt_set_bots: 0 (every object static) or n_obj rows of
+  // kWalkRec doubles behind `drivable` (walk_rows), then the bot header
   int32_t n_walk;
   const double* curves;     // [C,kCurveRec] ground-plane curve records (CurveRec)
   const double* obj;        // [n_obj, DT_OBJ_STRIDE] collidable static objects
@@ -97,7 +97,14 @@ struct MapDev {
 // object).
 constexpr int kWalkRec = 4;
 // The rows lie in the map's device allocation behind the drivable list
-// (dt_create leaves room for n_obj of them).
+// (dt_create leaves room for n_obj of them and the bot header).
+//
+// dt_set_bots: a bot row has bit 63 of that word set and the bot's column b of
+// the path table in its low half.  kBotHdr doubles follow the rows: the bits
+// of the table's device address ([rows, n_bots, DT_OBJ_STRIDE] f64, global
+// memory), then rows | n_bots << 32 (both 0 without bots).
+constexpr int kBotHdr = 2;
+constexpr uint64_t kBotMark = 1ull << 63;
 __host__ __device__ inline const double* walk_rows(const MapDev& m) {
   return reinterpret_cast<const double*>(reinterpret_cast<const unsigned char*>(m.drivable) +
                                          (((size_t)m.n_drivable * 2 + 15) & ~(size_t)15));
@@ -116,6 +123,10 @@ struct MapLds {
   const uint32_t* tinfo;
   int32_t width, height, n_drivable, n_obj, n_spawn_obj;
   const double* walk;   // [n_obj, kWalkRec]: only stage_map<true> sets it
+  // dt_set_bots (only stage_map<true, true> sets them): the path table in global
+  // memory, its rows and columns
+  const double* bots;
+  uint32_t bot_rows, n_bots;
 };
 
 __host__ __device__ inline size_t map_lds_bytes(int n_tiles, int n_drivable, int n_curves,
@@ -129,15 +140,18 @@ __host__ __device__ inline size_t map_lds_bytes(int n_tiles, int n_drivable, int
   b += (size_t)n_tiles * 4;
   // the walker rows lie behind everything else, so the image without them is
   // a prefix of the image with them (stage_map<false> of a handle with walkers)
-  if (n_walk > 0) b = ((b + 7) & ~(size_t)7) + (size_t)n_walk * kWalkRec * sizeof(double);
+  if (n_walk > 0)
+    b = ((b + 7) & ~(size_t)7) + ((size_t)n_walk * kWalkRec + kBotHdr) * sizeof(double);
   return b;
 }
 
 // Cooperative copy of the map into LDS; every thread of the block calls it.
 // kWalk: the walker rows too (the step kernels' walker instantiations; the
-// spawn code never reads them: a walker is at home at every reset).
-template <bool kWalk = false>
+// spawn code never reads them: a walker and a bot are at home at every reset).
+// kBot (with kWalk): the bot header behind them too.
+template <bool kWalk = false, bool kBot = false>
 __device__ inline MapLds stage_map(const MapDev& m, unsigned char* lds) {
+  static_assert(!kBot || kWalk, "the bot marks lie in the walker rows");
   double* cv = reinterpret_cast<double*>(lds);
   double* ob = cv + (size_t)m.n_curves * kCurveRec;
   double* so = ob + (size_t)m.n_obj * DT_OBJ_STRIDE;
@@ -163,11 +177,20 @@ __device__ inline MapLds stage_map(const MapDev& m, unsigned char* lds) {
         lds + ((map_lds_bytes(m.n_tiles, m.n_drivable, m.n_curves, m.n_obj, m.n_spawn_obj) + 7) &
                ~(size_t)7));
     const double* src = walk_rows(m);
-    for (int i = tid; i < m.n_walk * kWalkRec; i += nt) wk[i] = src[i];
+    for (int i = tid; i < m.n_walk * kWalkRec + (kBot ? kBotHdr : 0); i += nt) wk[i] = src[i];
   }
   __syncthreads();
   MapLds r;
   r.walk = wk;
+  r.bots = nullptr;
+  r.bot_rows = r.n_bots = 0u;
+  if (kBot) {
+    const double* hd = wk + (size_t)m.n_walk * kWalkRec;
+    const uint64_t rn = (uint64_t)__double_as_longlong(hd[1]);
+    r.bots = reinterpret_cast<const double*>((uintptr_t)__double_as_longlong(hd[0]));
+    r.bot_rows = (uint32_t)rn;
+    r.n_bots = (uint32_t)(rn >> 32);
+  }
   r.curves = cv;
   r.obj = ob;
   r.spawn_obj = so;
@@ -304,6 +327,55 @@ __device__ inline bool drivable_fast(const MapLds& M, const Geo& g, double x, do
 // the shift (false for a static row); collide and proximity_penalty translate
 // the row's corners / centre by it, one add each, and collide takes the row's
 // own projections from the translated corners instead of the record.
+//
+// dt_set_bots: a bot row's record at step count t is row min(t, rows - 1) of
+// the path table in global memory (bot_record; nullptr for any other row).
+// The static row's code then runs on that record unchanged.  kBot: the
+// instantiations that look for bot rows (with kWalk: the rows are staged).
+__device__ inline const double* bot_record(const MapLds& M, int o, uint32_t t) {
+  const uint64_t wk = (uint64_t)__double_as_longlong(M.walk[(size_t)o * kWalkRec + 3]);
+  if ((wk & kBotMark) == 0u) return nullptr;   // uniform
+  const uint32_t tt = t < M.bot_rows - 1u ? t : M.bot_rows - 1u;   // the clamp (dtsim.h)
+  return M.bots + ((size_t)tt * M.n_bots + (uint32_t)wk) * DT_OBJ_STRIDE;
+}
+
+// A bot's record against the agent's box, as collide's static row code below
+// (kept apart from it so that the instantiations without movers compile to
+// what they always did): true when an axis separates them.  amin / amax: the
+// agent on its own axes (f, r); ax / az: its corners.
+__device__ __forceinline__ bool bot_separated(const double* ob, double fx, double fz, double rx,
+                                              double rz, const double (&ax)[4],
+                                              const double (&az)[4], const double (&amin)[2],
+                                              const double (&amax)[2]) {
+  bool sep = false;
+  // the object's corners on the agent's axes
+#pragma unroll
+  for (int a = 0; a < 2 && !sep; ++a) {
+    const double nx = a == 0 ? fx : rx, nz = a == 0 ? fz : rz;
+    double lo = ob[DT_OBJ_CORNERS] * nx + ob[DT_OBJ_CORNERS + 1] * nz, hi = lo;
+#pragma unroll
+    for (int k = 1; k < 4; ++k) {
+      const double p = ob[DT_OBJ_CORNERS + 2 * k] * nx + ob[DT_OBJ_CORNERS + 2 * k + 1] * nz;
+      lo = p < lo ? p : lo;
+      hi = p > hi ? p : hi;
+    }
+    sep = amax[a] < lo || hi < amin[a];
+  }
+  // the agent's corners on the object's axes
+#pragma unroll
+  for (int a = 0; a < 2 && !sep; ++a) {
+    const double nx = ob[DT_OBJ_NORMS + 2 * a], nz = ob[DT_OBJ_NORMS + 2 * a + 1];
+    double lo = ax[0] * nx + az[0] * nz, hi = lo;
+#pragma unroll
+    for (int k = 1; k < 4; ++k) {
+      const double p = ax[k] * nx + az[k] * nz;
+      lo = p < lo ? p : lo;
+      hi = p > hi ? p : hi;
+    }
+    sep = hi < ob[DT_OBJ_PROJ + 2 * a] || ob[DT_OBJ_PROJ + 2 * a + 1] < lo;
+  }
+  return sep;
+}
 __device__ inline bool walk_shift(const MapLds& M, int o, uint32_t t, double& dx, double& dz) {
   const double* w = M.walk + (size_t)o * kWalkRec;
   const uint64_t wk = (uint64_t)__double_as_longlong(w[3]);
@@ -318,9 +390,10 @@ __device__ inline bool walk_shift(const MapLds& M, int o, uint32_t t, double& dx
   return true;
 }
 
-template <bool kWalk = false>
+template <bool kWalk = false, bool kBot = false>
 __device__ inline bool collide(const MapLds& M, const Geo& g, double px, double pz, double c,
                                double s, uint32_t t = 0u) {
+  static_assert(!kBot || kWalk, "the bot marks lie in the walker rows");
   if (M.n_obj == 0) return false;
   const double fx = c, fz = -s, rx = s, rz = c;   // get_dir_vec, get_right_vec
   const double hw = g.robot_width * 0.5, hl = g.robot_length * 0.5;
@@ -350,6 +423,12 @@ __device__ inline bool collide(const MapLds& M, const Geo& g, double px, double 
   for (int o = 0; o < M.n_obj; ++o) {
     const double* ob = M.obj + (size_t)o * DT_OBJ_STRIDE;
     bool sep = false;
+    if (kBot) {   // (first: a bot row's word is no walker's W | K)
+      if (const double* bt = bot_record(M, o, t)) {   // a bot's record at time t
+        if (!bot_separated(bt, fx, fz, rx, rz, ax, az, amin, amax)) return true;
+        continue;
+      }
+    }
     double wdx = 0.0, wdz = 0.0;
     if (kWalk && walk_shift(M, o, t, wdx, wdz)) {
       double wx[4], wz[4];
@@ -423,17 +502,24 @@ __device__ inline bool collide(const MapLds& M, const Geo& g, double px, double 
 // proximity_penalty2 at the actual centre: the sum of the negative
 // (|c_o - p| - AGENT_SAFETY_RAD - r_o) over the collidable objects
 // (safety_circle_overlap; 0 when no safety circle meets the agent's)
-template <bool kWalk = false>
+template <bool kWalk = false, bool kBot = false>
 __device__ inline double proximity_penalty(const MapLds& M, const Geo& g, double px, double pz,
                                            uint32_t t = 0u) {
+  static_assert(!kBot || kWalk, "the bot marks lie in the walker rows");
   double pen = 0.0;
   for (int o = 0; o < M.n_obj; ++o) {
     const double* ob = M.obj + (size_t)o * DT_OBJ_STRIDE;
     double ox = ob[DT_OBJ_CENTER], oz = ob[DT_OBJ_CENTER + 2];
     double wdx = 0.0, wdz = 0.0;
-    if (kWalk && walk_shift(M, o, t, wdx, wdz)) {   // a walker's centre at time t
+    const double* bt = nullptr;
+    if (kBot) bt = bot_record(M, o, t);   // (a bot row's word is no walker's W | K)
+    if (kWalk && !bt && walk_shift(M, o, t, wdx, wdz)) {   // a walker's centre at time t
       ox = ox + wdx;
       oz = oz + wdz;
+    }
+    if (kBot && bt) {   // a bot's centre at time t
+      ox = bt[DT_OBJ_CENTER];
+      oz = bt[DT_OBJ_CENTER + 2];
     }
     const double dx = ox - px, dy = ob[DT_OBJ_CENTER + 1] - 0.0, dz = oz - pz;
     const double d = sqrt((dx * dx + dy * dy) + dz * dz);
@@ -457,7 +543,7 @@ __device__ inline bool inconvenient_spawn(const MapLds& M, double x, double z) {
 // _valid_pose with precomputed (c, s) = (cos, sin)(angle) (A6): the centre and
 // both wheels and the front drivable (scaled by safety) and no collision (the
 // unscaled agent box)
-template <bool kWalk = false>
+template <bool kWalk = false, bool kBot = false>
 __device__ inline bool valid_pose(const MapLds& M, const Geo& g, double x, double z, double c,
                                   double s, double safety, uint32_t t = 0u) {
   const double px = x + g.off * c;
@@ -471,7 +557,7 @@ __device__ inline bool valid_pose(const MapLds& M, const Geo& g, double x, doubl
   const bool d2 = drivable(M, g, px + kw * s, pz + kw * c);
   const bool d3 = drivable(M, g, px + kf * c, pz + kf * (-s));
   const bool ok = d0 & d1 & d2 & d3;
-  return ok && !collide<kWalk>(M, g, px, pz, c, s, t);
+  return ok && !collide<kWalk, kBot>(M, g, px, pz, c, s, t);
 }
 
 // valid_pose without the collision test: the four drivable probes (fast form)
@@ -752,14 +838,15 @@ __device__ inline bool probe_q(const MapLds& M, const Geo& g, int q, double x, d
 
 // _valid_pose at one pose over a quad, identical to valid_pose (kObj false:
 // the caller guarantees a map without collidable objects)
-template <bool kObj = true, bool kWalk = false>
+template <bool kObj = true, bool kWalk = false, bool kBot = false>
 __device__ inline bool valid_pose_q(const MapLds& M, const Geo& g, int q, double x, double z,
                                     double c, double s, double safety, uint32_t t = 0u) {
   bool near = false;
   bool ok = qall(probe_q(M, g, q, x, z, c, s, safety, near));
-  if (__builtin_expect(qany(near), 0)) return valid_pose<kWalk>(M, g, x, z, c, s, safety, t);
+  if (__builtin_expect(qany(near), 0))
+    return valid_pose<kWalk, kBot>(M, g, x, z, c, s, safety, t);
   if (kObj && M.n_obj && ok)
-    ok = !collide<kWalk>(M, g, x + g.off * c, z + g.off * (-s), c, s, t);
+    ok = !collide<kWalk, kBot>(M, g, x + g.off * c, z + g.off * (-s), c, s, t);
   return ok;
 }
 

@@ -36,7 +36,15 @@ is a function of time alone, so here a walker's displacement is a closed form
 of the env's Simulator step counter (walker_index; include/dtsim.h
 dt_set_walkers restates it) and the walker is at home whenever the counter is
 0 -- upstream keeps its objects moving across resets; build-defined.  A walker
-is always collidable.  Any other kind with ``static: false`` is refused.
+is always collidable.
+
+Lane-following bots (upstream DuckiebotObj of the AIDO1 era, recalled; parity
+unpinned): a ``duckiebot`` with ``static: false`` drives along the lane centre
+by pure pursuit.  It reads nothing of the agent, so its pose after t Simulator
+steps from home is a function of t alone -- a table the device computes once
+(dt_bot_path, include/dtsim.h) and the step and render kernels index with the
+env's step counter.  Opt-in: ``load_map(..., lane_bots=True)``; without the
+switch such an entry is refused, as is any other kind with ``static: false``.
 """
 import math
 import os
@@ -47,6 +55,9 @@ import yaml
 
 MAP_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'maps')
 
+# the agent's box, which a moving bot takes (dt_config.robot_width / robot_length)
+ROBOT_WIDTH = 0.13 + 0.02
+ROBOT_LENGTH = 0.18
 SAFETY_RAD_MULT = 1.8
 MIN_SPAWN_OBJ_DIST = 0.25
 DEFAULT_FRAMERATE = 30
@@ -55,6 +66,14 @@ DEFAULT_FRAMERATE = 30
 WALKER_VEL = 0.02
 WALKER_WAIT = 8.0
 WALKER_EXTRA_DIST = 0.25
+# upstream DuckiebotObj defaults: metres a second, metres; then the constants of
+# its wheel controller (gain, trim, wheel radius, motor constant k, limit)
+BOT_VELOCITY = 0.1
+BOT_FOLLOW_DIST = 0.3
+BOT_GAIN, BOT_TRIM, BOT_RADIUS, BOT_K, BOT_LIMIT = 2.0, 0.0, 0.0318, 27.0, 1.0
+BOT_STRIDE = 7       # DT_BOT_STRIDE: velocity, follow_dist, gain, trim, radius, k, limit
+MAX_BOT_ROWS = 131072            # DT_MAX_BOT_ROWS
+MAX_BOT_BYTES = 256 << 20        # of the [rows, n, 20] float64 table
 # mesh bounding boxes (min, max) in mesh units, y up -- ASSUMED (the upstream
 # .obj meshes are absent); with `height` only their proportions matter
 MESH_EXTENTS = {
@@ -178,6 +197,31 @@ def find_candidate_tiles(corners, tile_size):
     return [(x, y) for x in range(mn[0], mx[0] + 1) for y in range(mn[1], mx[1] + 1)]
 
 
+def agent_boundbox(true_pos, width, length, f_vec, r_vec):
+    """Upstream agent_boundbox: the [4, 2] (x, z) corners of a width x length
+    box about true_pos (x, y, z) with forward / right vectors f_vec / r_vec."""
+    hwidth = width / 2
+    hlength = length / 2
+    return np.array([
+        true_pos - hwidth * r_vec - hlength * f_vec,
+        true_pos + hwidth * r_vec - hlength * f_vec,
+        true_pos + hwidth * r_vec + hlength * f_vec,
+        true_pos - hwidth * r_vec + hlength * f_vec,
+    ])[:, [0, 2]]
+
+
+def bot_rows(max_steps, frame_skip, max_env_steps):
+    """Rows of a bot path table that a wrapped run never leaves: the largest
+    Simulator step counter an episode reaches, plus row 0.  EnvironmentWrapper
+    counts Simulator.step calls (frame_skip updates each) and ends the episode
+    once the count exceeds max_env_steps; the Simulator ends it at the first
+    whole Simulator.step that reaches max_steps (so at max_steps rounded up to
+    a multiple of frame_skip)."""
+    fs = int(frame_skip)
+    by_sim = -(-int(max_steps) // fs) * fs
+    return min(by_sim, fs * (int(max_env_steps) + 1)) + 1
+
+
 def walker_index(t, W, K):
     """Steps of `vel` a walker stands from home at Simulator step count t: it
     waits W steps, walks K, waits W, walks K back, ... (period 2 (W + K)).
@@ -208,10 +252,23 @@ class MapObject:
     walk_distance: float = 0.0
     W: int = 0
     K: int = 0
+    # a lane-following bot (kind duckiebot, static false): metres a second, metres
+    velocity: float = 0.0
+    follow_dist: float = 0.0
+
+    @property
+    def bot(self):
+        return not self.static and self.kind == 'duckiebot'
 
     @property
     def walker(self):
-        return not self.static
+        return not self.static and not self.bot
+
+    @property
+    def bot_params(self):
+        """The DT_BOT_STRIDE doubles of dt_bot_path for this bot."""
+        return [self.velocity, self.follow_dist, BOT_GAIN, BOT_TRIM, BOT_RADIUS, BOT_K,
+                BOT_LIMIT]
 
     @property
     def heading(self):
@@ -272,11 +329,12 @@ def parse_object(desc, tile_size):
 
 def parse_walker(desc, tile_size, frame_rate=DEFAULT_FRAMERATE):
     """A walker: `kind: duckie` with `static: false`.  Any other dynamic kind
-    (the duckiebot follows a lane and reacts to the agent: per-env state and a
-    kernel of its own) is refused."""
+    is refused (the lane-following duckiebot is parse_bot's, behind
+    `lane_bots=True`)."""
     if bool(desc.get('static', True)) or desc['kind'] != 'duckie':
-        raise NotImplementedError('dynamic (non-static) objects of kind %r are not supported '
-                                  '(only the walking duckie is)' % desc['kind'])
+        raise NotImplementedError(
+            'dynamic (non-static) objects of kind %r are not supported (only the walking '
+            'duckie is, and with lane_bots=True the lane-following duckiebot)' % desc['kind'])
     obj = _parse_geometry(desc, tile_size)
     obj.vel = float(desc.get('vel', WALKER_VEL))
     obj.wait = float(desc.get('wait', WALKER_WAIT))
@@ -294,6 +352,23 @@ def parse_walker(desc, tile_size, frame_rate=DEFAULT_FRAMERATE):
     obj.K = k
     if obj.W >= 1 << 24 or obj.K >= 1 << 24:
         raise ValueError('walker wait / walk steps must stay below 2^24')
+    obj.collidable = True
+    return obj
+
+
+def parse_bot(desc, tile_size):
+    """A lane-following bot: `kind: duckiebot` with `static: false` (what
+    `lane_bots=True` sends here).  Its home is the entry's pose; its record at
+    home is the static object's."""
+    if bool(desc.get('static', True)) or desc['kind'] != 'duckiebot':
+        raise NotImplementedError('parse_bot takes a duckiebot with static: false, not %r'
+                                  % desc['kind'])
+    obj = _parse_geometry(desc, tile_size)
+    obj.velocity = float(desc.get('velocity', BOT_VELOCITY))
+    obj.follow_dist = float(desc.get('follow_dist', BOT_FOLLOW_DIST))
+    if not (obj.velocity >= 0.0 and math.isfinite(obj.velocity)) or \
+            not (obj.follow_dist > 0.0 and math.isfinite(obj.follow_dist)):
+        raise ValueError('bot needs a finite velocity >= 0 and a finite follow_dist > 0')
     obj.collidable = True
     return obj
 
@@ -318,17 +393,98 @@ class TileMap:
     @property
     def object_table(self):
         """[K, 20] float64 records of the collidable objects (dt_map.objects):
-        the static ones in load order, then the walkers (at home) in load order."""
+        the static ones in load order, then the walkers, then the bots (both at
+        home), each in load order."""
         recs = [o.record() for o in self._collidables()]
         return np.array(recs, np.float64).reshape(-1, 20)
 
     def _collidables(self):
         objs = [o for o in (self.objects or []) if o.collidable]
-        return [o for o in objs if not o.walker] + [o for o in objs if o.walker]
+        return [o for o in objs if o.static] + [o for o in objs if o.walker] + \
+            [o for o in objs if o.bot]
 
     @property
     def has_walkers(self):
         return any(o.walker for o in (self.objects or []))
+
+    @property
+    def bots(self):
+        """The bots in load order (the order of every bot table's columns)."""
+        return [o for o in (self.objects or []) if o.bot]
+
+    @property
+    def bot_home(self):
+        """[n, 3] float64 (x, z, angle) of the bots at home (dt_bot_path)."""
+        return np.array([[o.pos[0], o.pos[2], math.radians(o.rotate)] for o in self.bots],
+                        np.float64).reshape(-1, 3)
+
+    @property
+    def bot_param_table(self):
+        """[n, BOT_STRIDE] float64 (dt_bot_path)."""
+        return np.array([o.bot_params for o in self.bots], np.float64).reshape(-1, BOT_STRIDE)
+
+    @property
+    def bot_object_rows(self):
+        """[n] int32: each bot's row of object_table (dt_set_bots)."""
+        c = self._collidables()
+        return np.array([next(i for i, x in enumerate(c) if x is o) for o in self.bots], np.int32)
+
+    @property
+    def bot_render_rows(self):
+        """[n] int32: each bot's row of render_table (dt_render_bots)."""
+        objs = self.objects or []
+        return np.array([next(i for i, x in enumerate(objs) if x is o) for o in self.bots],
+                        np.int32)
+
+    def _bot_corners(self, path, robot_width=ROBOT_WIDTH, robot_length=ROBOT_LENGTH):
+        """[rows, n, 4, 2]: row 0 the bots' static corners, rows >= 1 the
+        agent_boundbox of the pose path[t, b] = (x, z, angle)."""
+        path = np.asarray(path, np.float64)
+        rows, n = path.shape[0], len(self.bots)
+        assert path.shape == (rows, n, 3), path.shape
+        out = np.zeros((rows, n, 4, 2), np.float64)
+        for b, o in enumerate(self.bots):
+            out[0, b] = o.corners
+            for t in range(1, rows):
+                x, z, a = path[t, b]
+                f = np.array([math.cos(a), 0.0, -math.sin(a)])
+                r = np.array([math.sin(a), 0.0, math.cos(a)])
+                out[t, b] = agent_boundbox(np.array([x, o.pos[1], z]), robot_width, robot_length,
+                                           f, r)
+        return out
+
+    def bot_records(self, path, robot_width=ROBOT_WIDTH, robot_length=ROBOT_LENGTH):
+        """[rows, n, 20] float64 (dt_set_bots): row 0 is record(); row t >= 1
+        holds the box upstream's DuckiebotObj._update_pos makes at path[t]:
+        corners = agent_boundbox(pos_t, robot_width, robot_length, dir, right),
+        axes = generate_norm of them, their projections, centre = pos_t; the
+        safety radius does not change."""
+        cor = self._bot_corners(path, robot_width, robot_length)
+        rows, n = cor.shape[:2]
+        out = np.zeros((rows, n, 20), np.float64)
+        for b, o in enumerate(self.bots):
+            out[0, b] = o.record()
+            for t in range(1, rows):
+                c = cor[t, b]
+                nm = generate_norm(c)
+                r = out[t, b]
+                r[0], r[1], r[2] = path[t, b, 0], o.pos[1], path[t, b, 1]
+                r[3] = o.safety_radius
+                r[4:12] = c.reshape(-1)
+                r[12:16] = nm.reshape(-1)
+                for a in range(2):
+                    r[16 + 2 * a:18 + 2 * a] = _proj(c, nm[a])
+        return out
+
+    def bot_render_records(self, path, robot_width=ROBOT_WIDTH, robot_length=ROBOT_LENGTH):
+        """[rows, n, 8] float32 (dt_render_bots): render_table's formula in
+        float64 on bot_records' corners, rounded once."""
+        cor = self._bot_corners(path, robot_width, robot_length)
+        c0, e1, e2 = cor[:, :, 0], cor[:, :, 1] - cor[:, :, 0], cor[:, :, 3] - cor[:, :, 0]
+        rec = np.concatenate([c0, e1, e2,
+                              (e1[..., 0] * e1[..., 0] + e1[..., 1] * e1[..., 1])[..., None],
+                              (e2[..., 0] * e2[..., 0] + e2[..., 1] * e2[..., 1])[..., None]], -1)
+        return rec.astype(np.float32)
 
     @property
     def walker_table(self):
@@ -390,7 +546,16 @@ def tile_curves(kind, orient, i, j, tile_size):
     return pts
 
 
-def parse_rows(rows, name='custom', tile_size=0.61, objects=(), frame_rate=DEFAULT_FRAMERATE):
+def _parse_entry(d, tile_size, frame_rate, lane_bots):
+    if d.get('static', True):
+        return parse_object(d, tile_size)
+    if lane_bots and d['kind'] == 'duckiebot':
+        return parse_bot(d, tile_size)
+    return parse_walker(d, tile_size, frame_rate)
+
+
+def parse_rows(rows, name='custom', tile_size=0.61, objects=(), frame_rate=DEFAULT_FRAMERATE,
+               lane_bots=False):
     H, W = len(rows), len(rows[0])
     kind = np.full(H * W, TILE_EMPTY, np.int8)
     orient = np.zeros(H * W, np.int8)
@@ -429,10 +594,9 @@ def parse_rows(rows, name='custom', tile_size=0.61, objects=(), frame_rate=DEFAU
         curves[a:b] = pts
         h = pts[:, -1, :] - pts[:, 0, :]          # closest_curve_point: one Frobenius norm
         headings[a:b] = h / np.linalg.norm(h).reshape(1, -1)
-    objs = [parse_object(d, tile_size) if d.get('static', True)
-            else parse_walker(d, tile_size, frame_rate) for d in objects]
+    objs = [_parse_entry(d, tile_size, frame_rate, lane_bots) for d in objects]
     for o in objs:   # _collidable_object: static, not a traffic light, meets a drivable tile
-        if o.kind == 'trafficlight' or o.walker:   # (a walker: always collidable)
+        if o.kind == 'trafficlight' or not o.static:   # (a walker, a bot: always collidable)
             continue
         for (ti, tj) in find_candidate_tiles(o.corners, tile_size):
             if 0 <= ti < W and 0 <= tj < H and kind[tj * W + ti] > 0 and sat_intersects(
@@ -444,7 +608,9 @@ def parse_rows(rows, name='custom', tile_size=0.61, objects=(), frame_rate=DEFAU
                    [list(r) for r in rows], objs)
 
 
-def load_map(name_or_path, tile_size=0.61, frame_rate=DEFAULT_FRAMERATE):
+def load_map(name_or_path, tile_size=0.61, frame_rate=DEFAULT_FRAMERATE, lane_bots=False):
+    """lane_bots: load `kind: duckiebot` entries with `static: false` as
+    lane-following bots (parse_bot); off, such an entry is refused."""
     path = name_or_path
     if not os.path.exists(path):
         path = os.path.join(MAP_DIR, name_or_path + '.yaml')
@@ -454,8 +620,20 @@ def load_map(name_or_path, tile_size=0.61, frame_rate=DEFAULT_FRAMERATE):
     if isinstance(objects, dict):   # newer map format: named objects
         objects = list(objects.values())
     name = os.path.splitext(os.path.basename(path))[0]
-    return parse_rows(doc['tiles'], name, tile_size, objects, frame_rate)
+    return parse_rows(doc['tiles'], name, tile_size, objects, frame_rate, lane_bots)
 
 
-def available_maps():
-    return sorted(os.path.splitext(f)[0] for f in os.listdir(MAP_DIR) if f.endswith('.yaml'))
+def _has_bots(path):
+    with open(path) as f:
+        objects = yaml.safe_load(f).get('objects') or []
+    if isinstance(objects, dict):
+        objects = list(objects.values())
+    return any(d.get('kind') == 'duckiebot' and not d.get('static', True) for d in objects)
+
+
+def available_maps(lane_bots=False):
+    """The shipped maps that load_map(name, lane_bots=lane_bots) loads: a map
+    with lane-following bots is listed only with the switch."""
+    names = sorted(os.path.splitext(f)[0] for f in os.listdir(MAP_DIR) if f.endswith('.yaml'))
+    return [n for n in names
+            if lane_bots or not _has_bots(os.path.join(MAP_DIR, n + '.yaml'))]

@@ -69,7 +69,7 @@ class Simulator:
                  camera_width=640, camera_height=480, accept_start_angle_deg=60,
                  full_transparency=False, distortion=False, frame_skip=1, draw_curve=False,
                  draw_bbox=False, robot_speed=None, frame_rate=30, device=None, env_id=0,
-                 draw_objects=False, **unsupported):
+                 draw_objects=False, lane_bots=False, bot_rows=None, **unsupported):
         if domain_rand:
             raise NotImplementedError('domain randomisation is not on the hot path '
                                       '(launch_env passes domain_rand=0, env.py:11)')
@@ -85,7 +85,7 @@ class Simulator:
         self.config = cfg
         self._seed = 0 if seed is None else int(seed)
         self._env = VecEnv(1, seed=self._seed, device=device, config=cfg, env_id_base=env_id,
-                           draw_objects=draw_objects)
+                           draw_objects=draw_objects, lane_bots=lane_bots, bot_rows=bot_rows)
         self._dev = self._env.device
         self._out = RenderOutput(1, self._dev, slots=1, rgb=True, masks=False)
         self._act = torch.zeros(1, 2, dtype=torch.float32, device=self._dev)

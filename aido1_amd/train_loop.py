@@ -79,7 +79,8 @@ class TrainLoop:
                  updates_per_step=1, refresh_every=1, obs_dtype=None, actor_dtype=torch.float32,
                  actor_mode='reference', masks=False, graph=True, overlap=False, n_exploit=None,
                  save_dir=None, log_dir=None, poll_every=0, check_every=0, frames='index',
-                 importance_weights=False, beta_decay=None, draw_objects=False):
+                 importance_weights=False, beta_decay=None, draw_objects=False,
+                 lane_bots=False):
         t = config['training']
         if importance_weights and not prioritized:
             raise ValueError('importance_weights needs prioritized=True (the weights are the '
@@ -105,7 +106,7 @@ class TrainLoop:
                                     env_id_base=env_id_base, actor=self.trainer.actor,
                                     dtype=actor_dtype, masks=masks, actor_mode=actor_mode,
                                     n_exploit=n_exploit, guard=self.guard, frames=frames,
-                                    draw_objects=draw_objects)
+                                    draw_objects=draw_objects, lane_bots=lane_bots)
         self.rollout.load_exploit_actor(self.trainer.target_actor)
         size = int(buffer_size or t['buffer_size'])
         gen = torch.Generator(device=self.device)

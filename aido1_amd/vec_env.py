@@ -20,7 +20,7 @@ import torch
 
 from aido1_amd import _lib
 from aido1_amd.config import EnvConfig
-from aido1_amd.maps import load_map
+from aido1_amd.maps import MAX_BOT_BYTES, MAX_BOT_ROWS, bot_rows as default_bot_rows, load_map
 
 _NULL = ctypes.c_void_p(0)
 
@@ -62,12 +62,23 @@ class VecEnv:
         (dt_render_walkers); such a handle renders one decision a launch
         (render_group_into is refused).
 
+      lane_bots: load the map's `kind: duckiebot`, `static: false` entries as
+        lane-following bots (maps.py; without it such a map is refused).  Their
+        paths are computed once on the device (dt_bot_path; `bot_path`,
+        [rows, n_bots, 3] x, z, angle) and every env's bots stand where its
+        step counter puts them, in collision and the reward (dt_set_bots) and,
+        with draw_objects, in the frame (dt_render_bots; one decision a
+        launch, as with walkers).
+      bot_rows: rows of the bots' tables; default maps.bot_rows of the config,
+        the most a wrapped episode can reach.  Past the last row a bot stands
+        still.
+
     A map with walkers always has them in collision and the reward
     (dt_set_walkers), whatever draw_objects says.
     """
 
     def __init__(self, n_envs, map_name=None, seed=123, device=None, config=None,
-                 env_id_base=0, draw_objects=False):
+                 env_id_base=0, draw_objects=False, lane_bots=False, bot_rows=None):
         self.config = config or EnvConfig()
         if map_name is not None:
             self.config = self.config.replace(map_name=map_name)
@@ -75,8 +86,20 @@ class VecEnv:
             device = torch.cuda.current_device() if torch.cuda.is_available() else 0
         self.device = torch.device('cuda', device)
         self.n = int(n_envs)
+        self.lane_bots = bool(lane_bots)
         self.map = load_map(self.config.map_name, self.config.road_tile_size,
-                            self.config.frame_rate)
+                            self.config.frame_rate, lane_bots=self.lane_bots)
+        self.bot_path = None
+        nb = len(self.map.bots)
+        if nb:
+            rows = int(bot_rows) if bot_rows is not None else default_bot_rows(
+                self.config.max_steps, self.config.frame_skip, self.config.max_env_steps)
+            if rows < 1 or rows > MAX_BOT_ROWS or rows * nb * 160 > MAX_BOT_BYTES:
+                raise ValueError(
+                    'the bots\' table would have %d rows x %d bots (at most %d rows and %d '
+                    'bytes): lower max_steps / max_env_steps or pass bot_rows= explicitly'
+                    % (rows, nb, MAX_BOT_ROWS, MAX_BOT_BYTES))
+            self._bot_rows = rows
         self.env_id_base = int(env_id_base)
         self._L = _lib.lib()
         cfg = self.config.to_c()
@@ -103,6 +126,8 @@ class VecEnv:
             walk = np.ascontiguousarray(self.map.walker_table, np.float64)
             rc = self._L.dt_set_walkers(self._h, walk.ctypes.data_as(ctypes.c_void_p), len(walk))
             _lib.check(self._L, self._h, rc, 'dt_set_walkers')
+        if nb:
+            self._upload_bots(cfg)
         self.draw_objects = bool(draw_objects)
         table = np.ascontiguousarray(self.map.render_table, np.float32)
         if self.draw_objects and len(table):   # (a map without objects: nothing to draw)
@@ -114,9 +139,35 @@ class VecEnv:
                 rc = self._L.dt_render_walkers(self._h, walk.ctypes.data_as(ctypes.c_void_p),
                                                len(walk))
                 _lib.check(self._L, self._h, rc, 'dt_render_walkers')
+            if nb:
+                rec = np.ascontiguousarray(self.map.bot_render_records(
+                    self.bot_path, cfg.robot_width, cfg.robot_length), np.float32)
+                row = np.ascontiguousarray(self.map.bot_render_rows, np.int32)
+                rc = self._L.dt_render_bots(self._h, rec.ctypes.data_as(ctypes.c_void_p),
+                                            row.ctypes.data_as(ctypes.c_void_p), len(rec), nb)
+                _lib.check(self._L, self._h, rc, 'dt_render_bots')
         self.seed(seed)
         self.out = StepOutput(self.n, self.device)
         self._reset_obs = torch.zeros(self.n, 2, dtype=torch.float32, device=self.device)
+
+    def _upload_bots(self, cfg):
+        """dt_bot_path on the handle's map, then the records of every step
+        (maps.TileMap.bot_records) into dt_set_bots."""
+        nb, rows = len(self.map.bots), self._bot_rows
+        home = np.ascontiguousarray(self.map.bot_home, np.float64)
+        par = np.ascontiguousarray(self.map.bot_param_table, np.float64)
+        path = np.zeros((rows, nb, 3), np.float64)
+        rc = self._L.dt_bot_path(self._h, home.ctypes.data_as(ctypes.c_void_p),
+                                 par.ctypes.data_as(ctypes.c_void_p), nb, rows,
+                                 path.ctypes.data_as(ctypes.c_void_p))
+        _lib.check(self._L, self._h, rc, 'dt_bot_path')
+        self.bot_path = path
+        rec = np.ascontiguousarray(
+            self.map.bot_records(path, cfg.robot_width, cfg.robot_length), np.float64)
+        row = np.ascontiguousarray(self.map.bot_object_rows, np.int32)
+        rc = self._L.dt_set_bots(self._h, rec.ctypes.data_as(ctypes.c_void_p),
+                                 row.ctypes.data_as(ctypes.c_void_p), rows, nb)
+        _lib.check(self._L, self._h, rc, 'dt_set_bots')
 
     # ---- helpers --------------------------------------------------------------
     def _stream(self):

@@ -17,8 +17,8 @@
  *     Pointers documented "host" are ordinary host memory.
  *   - All device work is enqueued on the given stream (hipStream_t passed as
  *     void*; NULL = the default stream).  Only dt_get_state / dt_set_state /
- *     dt_seed / dt_render_objects / dt_set_walkers / dt_render_walkers
- *     synchronise.
+ *     dt_seed / dt_render_objects / dt_set_walkers / dt_render_walkers /
+ *     dt_bot_path / dt_set_bots / dt_render_bots synchronise.
  *   - One handle per (process, GPU).  Calls on one handle are not thread-safe.
  */
 #ifndef AIDO1_AMD_DTSIM_H
@@ -65,7 +65,10 @@ extern "C" {
                                 dt_set_walkers, dt_render_walkers (additive:
                                 walking duckies in collision, reward and the
                                 frame; dt_map and dt_render_io keep their
-                                layouts, a handle without them is unchanged) */
+                                layouts, a handle without them is unchanged);
+                                dt_bot_path, dt_set_bots, dt_render_bots
+                                (additive: lane-following duckiebots, the same
+                                way) */
 
 /* error codes */
 #define DT_OK 0
@@ -400,7 +403,7 @@ int dt_render_objects(dt_handle* h, const float* recs, int32_t n);
  *         static object
  *   n     0 (off: every object static, as a new handle) or the handle's n_objects
  * The walker rows are staged in LDS behind the map image, which grows by
- * n * 32 bytes and must stay within the 48 KB dt_create allows.
+ * n * 32 + 16 bytes and must stay within the 48 KB dt_create allows.
  * Synchronous (waits for the device, then uploads into a buffer the handle
  * owns; nothing changes host-side per launch afterwards, so a captured graph
  * keeps replaying correctly as long as n stays).  DT_E_ARG, with dt_last_error
@@ -428,9 +431,118 @@ int dt_set_walkers(dt_handle* h, const double* recs, int32_t n);
  * walkers off (n = 0).  Synchronous.  DT_E_ARG, with dt_last_error set and
  * nothing changed, for: n neither 0 nor that count, recs NULL with n > 0, a
  * non-finite value, K < 1 on a non-zero row, a W or K that is negative, not
- * integral or not below 2^24. */
+ * integral or not below 2^24, or a non-zero row on a record dt_render_bots
+ * has made a bot's. */
 #define DT_RENDER_WALK_STRIDE 4
 int dt_render_walkers(dt_handle* h, const float* recs, int32_t n);
+
+/* ---- bots: lane-following duckiebots (upstream DuckiebotObj, AIDO1 era) -----
+ * Recalled from upstream, gym-duckietown being absent: parity is unpinned, as
+ * for the static objects and the walkers.  The AIDO1-era DuckiebotObj.step is a
+ * pure-pursuit follower of the lane centre that reads nothing of the agent, so
+ * a bot's pose after t Simulator steps from home depends on t alone: the same
+ * table for every env, indexed by the env's step_count.  No per-env object
+ * state; a bot is at home whenever step_count == 0, and every reset path sees
+ * the map with the bot standing at home as a static object (build-defined, as
+ * for the walkers).  OUT OF SCOPE: later upstream versions make the bot stop
+ * for other objects; this bot reacts to nothing -- not to the agent, not to
+ * walkers, not to other bots.
+ *
+ * Map keys (aido1_amd/maps.py, behind load_map(..., lane_bots=True)).  A bot is
+ * an object with `kind: duckiebot` and `static: false`.  Optional keys:
+ * `velocity`, m/s, >= 0, default 0.1; `follow_dist`, m, > 0, default 0.3.
+ * Controller constants (upstream's constructor defaults): gain 2.0, trim 0.0,
+ * wheel radius 0.0318, k 27.0, limit 1.0.  wheel_dist, robot_width,
+ * robot_length and delta_time are dt_config's.  Home is pose 0: pos times the
+ * tile size, angle = radians(rotate).  A bot is always collidable.
+ *
+ * One Simulator step of a bot, float64 with no contraction, in numpy's
+ * operation order (dir(a) = (cos a, 0, -sin a), right(a) = (sin a, 0, cos a)):
+ *   1. (P, T) = closest_curve_point(pos, angle): get_lane_pos2's own -- the
+ *      tile of pos, the argmax heading among the tile's curves, the 8-level
+ *      bisection; P the curve point, T the unit tangent there.
+ *   2. L = follow_dist; up to 1000 times: F = P + T * L,
+ *      (C, _) = closest_curve_point(F, angle); stop at the first C that
+ *      exists (F on a drivable tile), else L *= 0.5.
+ *   3. v = C - pos; v /= |v|; steer = gain * -(right(angle) . v).
+ *   4. Wheels, SteeringToWheelVelWrapper.action on (velocity, steer):
+ *      k_inv = (gain +- trim) / k; w = (velocity +- 0.5 * steer * wheel_dist)
+ *      / radius (+ right, - left); u = w * k_inv clamped to +-limit;
+ *      vels = [u_l, u_r].
+ *   5. Pose: the Simulator's _update_pos(pos, angle, wheel_dist, vels,
+ *      delta_time); vels as given, not multiplied by robot_speed.
+ * The path is undefined, and dt_bot_path fails, if at some step 1 finds no
+ * curve (the bot left the drivable tiles), 2 ends without a C, or a value is
+ * not finite.
+ *
+ * The box.  Row 0 of a bot's records is its static record (generate_corners
+ * of its mesh extents: dt_map.objects' row).  Row t >= 1 holds corners =
+ * agent_boundbox(pos_t, robot_width, robot_length, dir(angle_t),
+ * right(angle_t)), axes = generate_norm of them, their projections, centre =
+ * pos_t, the safety radius unchanged (upstream DuckiebotObj._update_pos).
+ * Which t: the walkers' rules -- _valid_pose and proximity_penalty2 use the
+ * counter after its increment; the render uses step_count[e] as the decision
+ * left it (0 after an auto-reset).  Past the table: every kernel reads row
+ * min(t, rows - 1), so a bot stays where the last row puts it (defined
+ * behaviour, and the memory-safety guard).  In dt_map.objects the bots follow
+ * the walkers, in load order. */
+#define DT_BOT_STRIDE 7          /* velocity, follow_dist, gain, trim, radius, k, limit */
+#define DT_MAX_BOT_ROWS 131072
+#define DT_MAX_BOT_BYTES 268435456   /* of dt_set_bots' / dt_render_bots' table */
+
+/* Compute n bots' paths on the handle's map (one device kernel, launched in
+ * chunks of <= 8192 steps) and return them.
+ *   home       host [n, 3] f64: x, z, angle at step 0
+ *   params     host [n, DT_BOT_STRIDE] f64
+ *   n          1..DT_MAX_RENDER_OBJECTS;  rows 1..DT_MAX_BOT_ROWS
+ *   path_host  host [rows, n, 3] f64 out: x, z, angle at t = 0..rows-1
+ * Synchronous; the handle does not change.  DT_E_ARG, with dt_last_error set
+ * (naming the bot and the step) and path_host untouched, for: n or rows out of
+ * range, a NULL pointer, a non-finite value, velocity < 0, follow_dist <= 0,
+ * radius <= 0, k <= 0, limit < 0, a path (rows * n * 24 bytes) over
+ * DT_MAX_BOT_BYTES, or an undefined path. */
+int dt_bot_path(dt_handle* h, const double* home, const double* params, int32_t n, int32_t rows,
+                double* path_host);
+
+/* Make rows of dt_map.objects follow a table.
+ *   recs        host [rows, n, DT_OBJ_STRIDE] f64: bot b's record at step t
+ *   object_row  host [n] i32: bot b's row of dt_map.objects
+ *   n           0 switches the bots off (recs, object_row, rows ignored)
+ * The step kernels then read a bot row's record from the table (device
+ * memory) at min(step count, rows - 1) and run the static row's code on it.
+ * Synchronous; the table's address reaches the kernels through device memory,
+ * so a graph captured with bots (or walkers) on keeps replaying correctly
+ * after any later upload -- n = 0 included: the rows are cleared before the
+ * table is freed, and the graph then sees every object static.  The map image in LDS grows by n_objects * 32 + 16
+ * bytes when a handle has walkers or bots.  DT_E_ARG, with dt_last_error set
+ * and nothing changed, for: n outside 0..n_objects, rows outside
+ * 1..DT_MAX_BOT_ROWS, a NULL pointer with n > 0, a row index outside
+ * n_objects or repeated, an index naming a walker row (and dt_set_walkers
+ * refuses a walker on a bot's row), a non-finite value, a table over
+ * DT_MAX_BOT_BYTES, or a map image over the LDS budget. */
+int dt_set_bots(dt_handle* h, const double* recs, const int32_t* object_row, int32_t rows,
+                int32_t n);
+
+/* Make records of dt_render_objects follow a table in the frame.
+ *   recs        host [rows, n, DT_RENDER_OBJ_STRIDE] f32: bot b's footprint
+ *               record at step t (dt_render_objects' formula on that step's
+ *               corners, in float64, rounded once)
+ *   render_row  host [n] i32: bot b's record of dt_render_objects
+ *   n           0 switches them off
+ * The render's phase 0c takes a bot's whole record from the table at
+ * min(step_count[e], rows - 1) -- the handle's current step_count, also when
+ * dt_render_io.pose is set.  dt_render2 / dt_render3 on a handle with render
+ * bots return DT_E_ARG, as with render walkers.  A later dt_render_objects
+ * with another count switches the bots off.  Synchronous.  Each upload
+ * allocates its table and frees the one before, and the table's address is a
+ * launch argument of dt_render: capture a graph that renders after this
+ * call, not before it.  DT_E_ARG, with
+ * dt_last_error set and nothing changed, for: n outside 0..that count, rows
+ * outside 1..DT_MAX_BOT_ROWS, a NULL pointer with n > 0, an index outside
+ * that count or repeated, an index naming a render walker's row, a
+ * non-finite value, or a table over DT_MAX_BOT_BYTES. */
+int dt_render_bots(dt_handle* h, const float* recs, const int32_t* render_row, int32_t rows,
+                   int32_t n);
 
 /* Diagnostics of that dispatch order (synchronises): launches so far, each
  * env's last recorded cost (shader cycles) and the order the next launch

@@ -2,9 +2,11 @@
 dt_step (config 2: 4096 envs, loop_empty, U[0,1)^2 actions).
 
   python tools/step_many_probe.py [--decisions 480] [--map NAME_OR_PATH] [--no-graph]
+                                  [--lane-bots]
 
 --map: another map (a name in aido1_amd/maps or a map file), e.g.
 loop_pedestrians against its all-static twin: the walkers' cost in the step.
+--lane-bots: load the map's lane-following duckiebots (loop_dyn_duckiebots).
 """
 import argparse
 import json
@@ -21,6 +23,7 @@ def main():
     p.add_argument('--ks', default='1,4,8,16,30,60,120')
     p.add_argument('--map', default='loop_empty')
     p.add_argument('--no-graph', action='store_true', help='skip the dt_step graphs')
+    p.add_argument('--lane-bots', action='store_true')
     args = p.parse_args()
     import torch
     from aido1_amd.config import EnvConfig
@@ -32,7 +35,8 @@ def main():
     acts = torch.rand(D + 30, n, 2, generator=g, device=dev)
     res = {}
     for k in [int(v) for v in args.ks.split(',')]:
-        env = VecEnv(n, seed=1234, device=0, config=EnvConfig(map_name=args.map))
+        env = VecEnv(n, seed=1234, device=0, config=EnvConfig(map_name=args.map),
+                     lane_bots=args.lane_bots)
         env.reset()
         out = StepOutput(k * n, dev, lanepos=False, tile=False)
         for i in range(30):
@@ -53,7 +57,8 @@ def main():
     if args.no_graph:
         print(json.dumps(res, indent=1), flush=True)
         return
-    env = VecEnv(n, seed=1234, device=0, config=EnvConfig(map_name=args.map))
+    env = VecEnv(n, seed=1234, device=0, config=EnvConfig(map_name=args.map),
+                 lane_bots=args.lane_bots)
     env.reset()
     out = StepOutput(n, dev, lanepos=False, tile=False)
     graphs = [env.capture(acts[30 + c * 30:30 + (c + 1) * 30], out) for c in range(D // 30)]
