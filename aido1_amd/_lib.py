@@ -177,11 +177,14 @@ def bind(L):
         'dt_step': (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         'dt_step_masked': (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         'dt_step_many': (ctypes.c_int, [vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+        'dt_step_many_time': (ctypes.c_int, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
         'dt_seed_env': (ctypes.c_int, [vp, i32, u64]),
         'dt_lane_pos': (ctypes.c_int, [vp, vp, vp, vp]),
         'dt_render': (ctypes.c_int, [vp, vp, vp]),
         'dt_render2': (ctypes.c_int, [vp, vp, vp, vp]),
         'dt_render3': (ctypes.c_int, [vp, vp, vp, vp, vp]),
+        'dt_render_group': (ctypes.c_int, [vp, vp, vp, i32, vp]),
+        'dt_copy_time': (ctypes.c_int, [vp, vp, vp]),
         'dt_render_objects': (ctypes.c_int, [vp, vp, i32]),
         'dt_set_walkers': (ctypes.c_int, [vp, vp, i32]),
         'dt_render_walkers': (ctypes.c_int, [vp, vp, i32]),

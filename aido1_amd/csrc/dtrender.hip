@@ -339,9 +339,13 @@ struct RenderArgs {
   const float4* objs;
   int32_t n_objs;
   // dt_render_walkers: a row per record (vel * hx, vel * hz, W, K; K = 0: the
-  // object is static), or null; the time is the env's Simulator step counter
+  // object is static), or null; the time is the env's Simulator step counter:
+  // decision 0's [n] (the handle's step_count, or dt_render_group's times[0]),
+  // decisions 1 and 2 theirs (read by the kObj instantiations only)
   const float4* walk;
   const uint32_t* step_count;
+  const uint32_t* time2;
+  const uint32_t* time3;
   // dt_render_bots (the kObj = 2 kernels): the table [bot_rows, n_bots] of
   // two-float4 records and each record's column of it (-1: not a bot)
   const float4* bots;
@@ -1313,11 +1317,12 @@ __device__ inline bool object_box(const View& V, float4 qa, float4 qb, uint2& bo
 // needs.
 template <bool kBot>
 __device__ __forceinline__ void draw_objects(const RenderArgs& a, RenderLds& S, const View& V,
-                                             int e) {
+                                             int e, int half) {
   const int tid = opaque_tid();
   constexpr int T = kRenderThreads;
-  // dt_render_walkers (uniform branch): the env's time, as the decision left it
-  const uint32_t t = (kBot || a.walk) ? a.step_count[e] : 0u;
+  // dt_render_walkers (uniform branch): the env's time, as this decision left it
+  const uint32_t* const tp = half == 0 ? a.step_count : (half == 1 ? a.time2 : a.time3);
+  const uint32_t t = (kBot || a.walk) ? tp[e] : 0u;
   for (int o0 = 0; o0 < a.n_objs; o0 += T) {
     const int o = o0 + tid;
     float4 qa, qb;
@@ -1550,7 +1555,7 @@ __device__ __forceinline__ void render_env(const RenderArgs& a, RenderLds& S, in
     }
   }
   __syncthreads();
-  if (kObj) draw_objects<kObj == 2>(a, S, V, e);
+  if (kObj) draw_objects<kObj == 2>(a, S, V, e, half);
   RENT(6);
   RENDER_STOP(2);
 
@@ -2167,8 +2172,11 @@ int dt_set_line_params(dt_handle* h, const dt_line_params* p) {
   return DT_OK;
 }
 
+// times: each decision's [n] step counters (device), or null entries / null =
+// the handle's current step_count
 static int render_launch(dt_handle* h, const dt_render_io* io, const dt_render_io* io2,
-                         const dt_render_io* io3, void* stream);
+                         const dt_render_io* io3, void* stream,
+                         const uint32_t* const* times = nullptr);
 
 int dt_render(dt_handle* h, const dt_render_io* io, void* stream) {
   return render_launch(h, io, nullptr, nullptr, stream);
@@ -2215,8 +2223,38 @@ int dt_render3(dt_handle* h, const dt_render_io* io_a, const dt_render_io* io_b,
   return render_launch(h, io_a, io_b, io_c, stream);
 }
 
+int dt_render_group(dt_handle* h, const dt_render_io* const* ios, const uint32_t* const* times,
+                    int32_t parts, void* stream) {
+  if (!h) return DT_E_ARG;
+  if (parts < 1 || parts > 3 || !ios) {
+    h->err = "dt_render_group: 1 to 3 decisions, ios given";
+    return DT_E_ARG;
+  }
+  for (int p = 0; p < parts; ++p)
+    if (!ios[p]) {
+      h->err = "dt_render_group: every decision's dt_render_io is required";
+      return DT_E_ARG;
+    }
+  if (parts == 1) return render_launch(h, ios[0], nullptr, nullptr, stream, times);
+  if (h->n_render_walk > 0 || h->n_render_bots > 0)
+    for (int p = 0; p < parts; ++p)
+      if (!times || !times[p]) {
+        h->err = "dt_render_group: each decision's time is required on a handle with render "
+                 "walkers or bots (dt_step_many_time's output, or dt_copy_time snapshots)";
+        return DT_E_ARG;
+      }
+  for (int p = 0; p < parts; ++p)
+    for (int q = p + 1; q < parts; ++q)
+      if (!group_ok(ios[p], ios[q])) {
+        h->err = "dt_render_group: decisions of one ring: poses given, the same ring, "
+                 "different slots, separate masks, no rgb";
+        return DT_E_ARG;
+      }
+  return render_launch(h, ios[0], ios[1], parts == 3 ? ios[2] : nullptr, stream, times);
+}
+
 static int render_launch(dt_handle* h, const dt_render_io* io, const dt_render_io* io2,
-                         const dt_render_io* io3, void* stream) {
+                         const dt_render_io* io3, void* stream, const uint32_t* const* times) {
   if (!h || !io) return DT_E_ARG;
   if (io->gray && io->index) {
     h->err = "dt_render: gray and index are two formats of one frame ring: give one";
@@ -2306,7 +2344,10 @@ static int render_launch(dt_handle* h, const dt_render_io* io, const dt_render_i
   a.objs = (const float4*)h->render_objs;
   a.n_objs = h->n_render_objs;
   a.walk = h->n_render_walk > 0 ? (const float4*)h->render_walk : nullptr;
-  a.step_count = h->st.step_count;
+  // never null, whichever kernel runs: an entry not given is the handle's own
+  a.step_count = times && times[0] ? times[0] : h->st.step_count;
+  a.time2 = io2 && times && times[1] ? times[1] : h->st.step_count;
+  a.time3 = io3 && times && times[2] ? times[2] : h->st.step_count;
   const bool bots = a.n_objs > 0 && h->n_render_bots > 0;
   a.bots = bots ? (const float4*)h->render_bot_tab : nullptr;
   a.bot_col = (const int32_t*)h->render_bot_col;
@@ -2520,6 +2561,18 @@ int dt_render_order(dt_handle* h, uint32_t* launches, uint32_t* cost, int32_t* o
   if (order)
     HIP_OR_FAIL(h, hipMemcpy(order, base + kSchedHead + n * (1 + (h->render_launches & 1u)),
                              n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  return DT_OK;
+}
+
+int dt_copy_time(dt_handle* h, uint32_t* time, void* stream) {
+  if (!h) return DT_E_ARG;
+  if (!time) {
+    h->err = "dt_copy_time: time is required";
+    return DT_E_ARG;
+  }
+  DevGuard dg(h->device);
+  HIP_OR_FAIL(h, hipMemcpyAsync(time, h->st.step_count, (size_t)h->n * sizeof(uint32_t),
+                                hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return DT_OK;
 }
 

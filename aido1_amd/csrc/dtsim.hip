@@ -601,6 +601,7 @@ __global__ __launch_bounds__(kFanBlock) __attribute__((amdgpu_waves_per_eu(2, 2)
                                                              uint8_t* __restrict__ done_out,
                                                              float2* __restrict__ obs,
                                                              double* __restrict__ pose_out,
+                                                             uint32_t* __restrict__ time_out,
                                                              int n_step_blocks,
                                                              uint32_t max_attempts,
                                                              uint32_t map_lds_offset) {
@@ -924,6 +925,9 @@ __global__ __launch_bounds__(kFanBlock) __attribute__((amdgpu_waves_per_eu(2, 2)
         if (!(DTSIM_DIAG_SKIP_STORES & 2)) rewm[o] = trm;
       } else if (wave == 1) {
         if (!(DTSIM_DIAG_SKIP_STORES & 4)) done_out[o] = (uint8_t)dn;
+        // the Simulator step counter the decision leaves (0 after a respawn):
+        // the time a render of this decision draws its walkers and bots at
+        if (time_out) time_out[o] = reset_now ? 0u : step_count;
       } else if (wave == 2 && obs && !(DTSIM_DIAG_SKIP_STORES & 8)) {
         obs[o] = reset_now ? make_float2((float)rp[3], (float)rp[4])
                            : (inl_last ? make_float2((float)dist_last, (float)arad_last)
@@ -1732,6 +1736,12 @@ int dt_step(dt_handle* h, const float* actions, double* reward, double* reward_m
 
 int dt_step_many(dt_handle* h, int32_t k, const float* actions, double* reward,
                  double* reward_mod, uint8_t* done, float* obs, double* pose, void* stream) {
+  return dt_step_many_time(h, k, actions, reward, reward_mod, done, obs, pose, nullptr, stream);
+}
+
+int dt_step_many_time(dt_handle* h, int32_t k, const float* actions, double* reward,
+                      double* reward_mod, uint8_t* done, float* obs, double* pose, uint32_t* time,
+                      void* stream) {
   if (!h) return DT_E_ARG;
   if (k < 1 || !actions || !reward || !reward_mod || !done) {
     h->err = "dt_step_many: k >= 1, actions, reward, reward_mod and done are required";
@@ -1769,7 +1779,8 @@ int dt_step_many(dt_handle* h, int32_t k, const float* actions, double* reward,
                          h->geo,
                          h->sc, h->n, h->env_base, kk, (const float2*)actions + o, reward + o,
                          reward_mod + o, done + o, obs ? (float2*)obs + o : (float2*)nullptr,
-                         pose ? pose + 3 * o : (double*)nullptr, gs, h->sc.max_spawn_attempts,
+                         pose ? pose + 3 * o : (double*)nullptr,
+                         time ? time + o : (uint32_t*)nullptr, gs, h->sc.max_spawn_attempts,
                          (uint32_t)off);
       HIP_OR_FAIL(h, hipGetLastError());
     }
@@ -1777,10 +1788,11 @@ int dt_step_many(dt_handle* h, int32_t k, const float* actions, double* reward,
   }
   // the generic path (more than three Simulator steps per decision, or
   // frame_skip > 1): step_kernel over the k decisions, or one launch per
-  // decision when the poses are asked for
+  // decision when the poses or the step counters are asked for
   const int gs = (h->n + kBlock - 1) / kBlock;
-  for (int d0 = 0; d0 < k; d0 += pose ? 1 : k) {
-    const int kk = pose ? 1 : k;
+  const bool each = pose || time;
+  for (int d0 = 0; d0 < k; d0 += each ? 1 : k) {
+    const int kk = each ? 1 : k;
     const size_t o = (size_t)d0 * h->n;
     hipLaunchKernelGGL(step_kernel_of(h), dim3(gs + rb), dim3(kBlock), h->lds_bytes, s, h->st,
                        h->map, h->geo, h->sc, h->n, h->env_base, kk,
@@ -1790,6 +1802,9 @@ int dt_step_many(dt_handle* h, int32_t k, const float* actions, double* reward,
     HIP_OR_FAIL(h, hipGetLastError());
     if (pose)
       HIP_OR_FAIL(h, hipMemcpyAsync(pose + 3 * o, h->st.x, 3 * (size_t)h->n * sizeof(double),
+                                    hipMemcpyDeviceToDevice, s));
+    if (time)
+      HIP_OR_FAIL(h, hipMemcpyAsync(time + o, h->st.step_count, (size_t)h->n * sizeof(uint32_t),
                                     hipMemcpyDeviceToDevice, s));
   }
   return DT_OK;

@@ -165,27 +165,69 @@ def _render_io(env, out, fresh, pose, list_cap):
                     int(list_cap), ring if idx else None)
 
 
-def render_into(env, out, fresh=None, pose=None, list_cap=0):
+def check_time(env, time):
+    """A decision's step counters: a contiguous int32 [n] tensor on the env's
+    device (the u32 bits; a row of step_many_into's time output is one)."""
+    if not torch.is_tensor(time) or time.dtype != torch.int32 or not time.is_contiguous() or \
+            tuple(time.shape) != (env.n,) or time.device != env.device:
+        raise ValueError('time must be a contiguous int32 [%d] tensor on %s'
+                         % (env.n, env.device))
+    return time
+
+
+def _group_args(ios, time):
+    """dt_render_group's host arrays for the decisions `ios` and their times."""
+    k = len(ios)
+    io_arr = (ctypes.c_void_p * k)(*[ctypes.addressof(io) for io in ios])
+    t_arr = (ctypes.c_void_p * k)(*[t.data_ptr() for t in time])
+    return io_arr, t_arr, k
+
+
+def render_into(env, out, fresh=None, pose=None, list_cap=0, time=None):
     """Render every env's current pose (or `pose`, a [3, n] f64 x/z/angle
     snapshot from VecEnv.copy_pose) into `out`, advancing the frame ring.
+    time: optional [n] int32 step counters (VecEnv.copy_pose(pose, time=), or a
+    row of step_many_into's time output): the map's walkers and bots stand
+    where they put them (dt_render_group, one decision) instead of where the
+    handle's current step counters do.
     fresh: optional [n] u8 device tensor; nonzero -> the frame fills every slot
     (Transformer.reset semantics): pass the done flags of an auto-resetting
     step.  The first render after RenderOutput creation / restart() fills every
     slot of every env.  list_cap > 0 (tests only) forces the kernel's
     global-memory overflow path."""
+    if time is not None:
+        check_time(env, time)
     io = _render_io(env, out, fresh, pose, list_cap)
-    rc = env._L.dt_render(env._h, ctypes.byref(io), env._stream())
-    env._check(rc, 'dt_render')
+    if time is None:
+        rc = env._L.dt_render(env._h, ctypes.byref(io), env._stream())
+        env._check(rc, 'dt_render')
+    else:
+        io_arr, t_arr, _ = _group_args([io], [time])
+        rc = env._L.dt_render_group(env._h, io_arr, t_arr, 1, env._stream())
+        env._check(rc, 'dt_render_group')
     return out
 
 
-def bind_render(env, out, stream, fresh=None, pose=None):
-    """A zero-argument callable that launches render_into(out, fresh, pose) on
-    `stream` (a torch.cuda.Stream) with its ctypes arguments built once, for
-    timed loops.  The ring slot is taken (advanced) at bind time, so bind the
-    calls of consecutive decisions in their order.  Returns dt_render's status."""
+def bind_render(env, out, stream, fresh=None, pose=None, time=None):
+    """A zero-argument callable that launches render_into(out, fresh, pose,
+    time=time) on `stream` (a torch.cuda.Stream) with its ctypes arguments
+    built once, for timed loops.  The ring slot is taken (advanced) at bind
+    time, so bind the calls of consecutive decisions in their order.  Returns
+    dt_render's (with time: dt_render_group's) status."""
+    if time is not None:
+        check_time(env, time)
     io = _render_io(env, out, fresh, pose, 0)
-    fn, h, st = env._L.dt_render, env._h, ctypes.c_void_p(stream.cuda_stream)
+    h, st = env._h, ctypes.c_void_p(stream.cuda_stream)
+    if time is not None:
+        fn = env._L.dt_render_group
+        io_arr, t_arr, _ = _group_args([io], [time])
+        keep = (out, fresh, pose, time, io, io_arr, t_arr, stream)
+
+        def launch_time():
+            keep  # noqa: B018 (the buffers stay alive with the callable)
+            return fn(h, io_arr, t_arr, 1, st)
+        return launch_time
+    fn = env._L.dt_render
     ref = ctypes.byref(io)
     keep = (out, fresh, pose, io, stream)
 
@@ -195,12 +237,18 @@ def bind_render(env, out, stream, fresh=None, pose=None):
     return launch
 
 
-def _group_ios(env, out, masks, fresh, pose):
+def _group_ios(env, out, masks, fresh, pose, time=None):
     """The dt_render_io of 2 or 3 consecutive decisions of one ring: decision
     0 writes out.masks, decision i > 0 masks[i - 1]."""
     k = len(pose)
     if k not in (2, 3) or len(fresh) != k or len(masks) != k - 1:
         raise ValueError('a render group is 2 or 3 decisions (k - 1 extra masks buffers)')
+    if time is not None:
+        if len(time) != k:
+            raise ValueError('render group: a time per decision (%d given for %d)'
+                             % (len(time), k))
+        for t in time:
+            check_time(env, t)
     if out.masks is None or out.rgb is not None or any(
             m is None or m.shape != out.masks.shape or m.data_ptr() == out.masks.data_ptr()
             for m in masks) or len({m.data_ptr() for m in masks}) != len(masks):
@@ -213,26 +261,45 @@ def _group_ios(env, out, masks, fresh, pose):
     return ios
 
 
-def render_group_into(env, out, masks, fresh, pose):
+def render_group_into(env, out, masks, fresh, pose, time=None):
     """2 or 3 consecutive decisions' renders in ONE launch (dt_render2 /
     dt_render3): decision i of the lists (fresh[i], pose[i]) into ring slot
     after the newest + i, its masks into out.masks (i = 0) or masks[i - 1].
-    Every output equals render_into of each decision in order."""
-    ios = _group_ios(env, out, masks, fresh, pose)
+    Every output equals render_into of each decision in order.
+    time: a list of each decision's [n] int32 step counters (rows of
+    step_many_into's time output); the launch then goes through
+    dt_render_group, which a handle that draws walkers or bots requires
+    (without time it is refused there, as dt_render2 / dt_render3 are)."""
+    ios = _group_ios(env, out, masks, fresh, pose, time)
+    if time is not None:
+        io_arr, t_arr, k = _group_args(ios, time)
+        rc = env._L.dt_render_group(env._h, io_arr, t_arr, k, env._stream())
+        env._check(rc, 'dt_render_group')
+        return out
     fn = env._L.dt_render2 if len(ios) == 2 else env._L.dt_render3
     rc = fn(env._h, *[ctypes.byref(io) for io in ios], env._stream())
     env._check(rc, 'dt_render%d' % len(ios))
     return out
 
 
-def render2_into(env, out, masks_b, fresh_a, pose_a, fresh_b, pose_b):
+def render2_into(env, out, masks_b, fresh_a, pose_a, fresh_b, pose_b, time=None):
     """render_group_into of two decisions."""
-    return render_group_into(env, out, [masks_b], [fresh_a, fresh_b], [pose_a, pose_b])
+    return render_group_into(env, out, [masks_b], [fresh_a, fresh_b], [pose_a, pose_b], time)
 
 
-def bind_render_group(env, out, stream, masks, fresh, pose):
+def bind_render_group(env, out, stream, masks, fresh, pose, time=None):
     """bind_render for render_group_into (2 or 3 decisions, one launch)."""
-    ios = _group_ios(env, out, masks, fresh, pose)
+    ios = _group_ios(env, out, masks, fresh, pose, time)
+    if time is not None:
+        gfn = env._L.dt_render_group
+        io_arr, t_arr, k = _group_args(ios, time)
+        gh, gst = env._h, ctypes.c_void_p(stream.cuda_stream)
+        gkeep = (out, masks, fresh, pose, time, ios, io_arr, t_arr, stream)
+
+        def launch_time():
+            gkeep  # noqa: B018
+            return gfn(gh, io_arr, t_arr, k, gst)
+        return launch_time
     fn = env._L.dt_render2 if len(ios) == 2 else env._L.dt_render3
     refs = [ctypes.byref(io) for io in ios]
     h, st = env._h, ctypes.c_void_p(stream.cuda_stream)
@@ -244,9 +311,10 @@ def bind_render_group(env, out, stream, masks, fresh, pose):
     return launch
 
 
-def bind_render2(env, out, stream, masks_b, fresh_a, pose_a, fresh_b, pose_b):
+def bind_render2(env, out, stream, masks_b, fresh_a, pose_a, fresh_b, pose_b, time=None):
     """bind_render_group of two decisions."""
-    return bind_render_group(env, out, stream, [masks_b], [fresh_a, fresh_b], [pose_a, pose_b])
+    return bind_render_group(env, out, stream, [masks_b], [fresh_a, fresh_b], [pose_a, pose_b],
+                             time)
 
 
 def line_detect(bgr, params=None, hsv=False, stream=None):

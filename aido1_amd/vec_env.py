@@ -60,7 +60,8 @@ class VecEnv:
         without objects.  A map's walkers (maps.py: a duckie with `static:
         false`) are drawn where each env's step counter puts them
         (dt_render_walkers); such a handle renders one decision a launch
-        (render_group_into is refused).
+        (render_group_into is refused) unless each decision's time is passed
+        (step_many_into's time output, render_group_into(..., time=)).
 
       lane_bots: load the map's `kind: duckiebot`, `static: false` entries as
         lane-following bots (maps.py; without it such a map is refused).  Their
@@ -68,7 +69,7 @@ class VecEnv:
         [rows, n_bots, 3] x, z, angle) and every env's bots stand where its
         step counter puts them, in collision and the reward (dt_set_bots) and,
         with draw_objects, in the frame (dt_render_bots; one decision a
-        launch, as with walkers).
+        launch unless each decision's time is passed, as with walkers).
       bot_rows: rows of the bots' tables; default maps.bot_rows of the config,
         the most a wrapped episode can reach.  Past the last row a bot stands
         still.
@@ -241,7 +242,13 @@ class VecEnv:
         self._check(rc, 'dt_step')
         return out
 
-    def _check_many(self, actions, out, pose):
+    def _check_time(self, time, shape):
+        if time.dtype != torch.int32 or not time.is_contiguous() or \
+                tuple(time.shape) != shape or time.device != self.device:
+            raise ValueError('time must be a contiguous int32 %s tensor on %s'
+                             % (list(shape), self.device))
+
+    def _check_many(self, actions, out, pose, time=None):
         k = int(actions.shape[0]) if actions.dim() == 3 else 0
         if actions.dtype != torch.float32 or not actions.is_contiguous() or \
                 actions.device != self.device or k < 1 or tuple(actions.shape[1:]) != (self.n, 2):
@@ -255,33 +262,39 @@ class VecEnv:
                                  pose.device != self.device):
             raise ValueError('pose must be a contiguous float64 [k, 3, %d] tensor on %s'
                              % (self.n, self.device))
+        if time is not None:
+            self._check_time(time, (k, self.n))
         return k
 
-    def step_many_into(self, actions, out, pose=None):
+    def step_many_into(self, actions, out, pose=None, time=None):
         """k decisions in one launch (dt_step_many): actions [k, n, 2] f32 on the
         device, out a StepOutput(k * n, ...) whose entries of decision d are at
         [d * n:(d + 1) * n] (view them as [k, n]); lanepos/tile are not
         produced.  pose: optional [k, 3, n] f64, each decision's end pose (what
         a render of that decision draws: render_into(..., pose=pose[d])).
+        time: optional [k, n] int32 (the u32 bits), each env's Simulator step
+        counter as each decision left it (0 after a respawn): the time that
+        render draws the map's walkers and bots at (render_into(...,
+        pose=pose[d], time=time[d]), render_group_into(..., time=[...])).
         Same results as k step_into calls."""
-        k = self._check_many(actions, out, pose)
-        self._check(self._L.dt_step_many(self._h, k, _ptr(actions), _ptr(out.reward),
-                                         _ptr(out.reward_mod), _ptr(out.done), _ptr(out.obs),
-                                         _ptr(pose), self._stream()), 'dt_step_many')
+        k = self._check_many(actions, out, pose, time)
+        self._check(self._L.dt_step_many_time(
+            self._h, k, _ptr(actions), _ptr(out.reward), _ptr(out.reward_mod), _ptr(out.done),
+            _ptr(out.obs), _ptr(pose), _ptr(time), self._stream()), 'dt_step_many')
         return out
 
-    def bind_step_many(self, actions, out, pose=None, stream=None):
+    def bind_step_many(self, actions, out, pose=None, stream=None, time=None):
         """A zero-argument callable that launches step_many_into(actions, out,
-        pose) on `stream` (default: the current stream) with its ctypes
+        pose, time) on `stream` (default: the current stream) with its ctypes
         arguments built once (checked here): the launch then costs one foreign
         call, for timed loops.  The callable returns dt_step_many's status
         (0 = DT_OK)."""
-        k = self._check_many(actions, out, pose)
-        fn = self._L.dt_step_many
+        k = self._check_many(actions, out, pose, time)
+        fn = self._L.dt_step_many_time
         st = ctypes.c_void_p(stream.cuda_stream) if stream is not None else self._stream()
         args = (self._h, k, _ptr(actions), _ptr(out.reward), _ptr(out.reward_mod),
-                _ptr(out.done), _ptr(out.obs), _ptr(pose), st)
-        keep = (actions, out, pose, stream)
+                _ptr(out.done), _ptr(out.obs), _ptr(pose), _ptr(time), st)
+        keep = (actions, out, pose, time, stream)
 
         def launch():
             keep  # noqa: B018 (the tensors stay alive with the callable)
@@ -308,19 +321,24 @@ class VecEnv:
             return fn(*args)
         return launch
 
-    def bind_copy_pose(self, pose, stream):
-        """A zero-argument callable for copy_pose(pose) on `stream`."""
+    def bind_copy_pose(self, pose, stream, time=None):
+        """A zero-argument callable for copy_pose(pose, time) on `stream`."""
         if pose.dtype != torch.float64 or not pose.is_contiguous() or \
                 tuple(pose.shape) != (3, self.n) or pose.device != self.device:
             raise ValueError('pose must be a contiguous float64 [3, %d] tensor on %s'
                              % (self.n, self.device))
-        fn = self._L.dt_copy_pose
-        args = (self._h, _ptr(pose), ctypes.c_void_p(stream.cuda_stream))
-        keep = (pose, stream)
+        if time is not None:
+            self._check_time(time, (self.n,))
+        fn, fnt = self._L.dt_copy_pose, self._L.dt_copy_time
+        st = ctypes.c_void_p(stream.cuda_stream)
+        args = (self._h, _ptr(pose), st)
+        targs = (self._h, _ptr(time), st)
+        keep = (pose, time, stream)
 
         def launch():
             keep  # noqa: B018
-            return fn(*args)
+            rc = fn(*args)
+            return rc if rc != 0 or time is None else fnt(*targs)
         return launch
 
     def capture(self, actions, out=None, render=None):
@@ -345,21 +363,30 @@ class VecEnv:
         return lp, tile
 
     # ---- observation path (config 3) ----------------------------------------------------
-    def render_into(self, out, fresh=None, pose=None, list_cap=0):
+    def render_into(self, out, fresh=None, pose=None, list_cap=0, time=None):
         """Top-down raster + grey + line masks of every env's current pose (or of a
-        copy_pose snapshot) into a RenderOutput (see aido1_amd/render.py)."""
+        copy_pose snapshot, with its time) into a RenderOutput (see
+        aido1_amd/render.py)."""
         from aido1_amd.render import render_into
-        return render_into(self, out, fresh, pose, list_cap)
+        return render_into(self, out, fresh, pose, list_cap, time)
 
-    def copy_pose(self, pose):
+    def copy_pose(self, pose, time=None):
         """Enqueue a copy of every env's (x, z, angle) into pose, a contiguous
         float64 [3, n] device tensor (dt_copy_pose): the render of this decision
-        reads the snapshot while the next step runs on another stream."""
+        reads the snapshot while the next step runs on another stream.  With
+        time, a contiguous int32 [n] device tensor, also a copy of every env's
+        step counter (dt_copy_time): render_into(..., pose=pose, time=time)
+        then draws the walkers and bots where this decision left them."""
         if pose.dtype != torch.float64 or not pose.is_contiguous() or \
                 tuple(pose.shape) != (3, self.n) or pose.device != self.device:
             raise ValueError('pose must be a contiguous float64 [3, %d] tensor on %s'
                              % (self.n, self.device))
+        if time is not None:
+            self._check_time(time, (self.n,))
         self._check(self._L.dt_copy_pose(self._h, _ptr(pose), self._stream()), 'dt_copy_pose')
+        if time is not None:
+            self._check(self._L.dt_copy_time(self._h, _ptr(time), self._stream()),
+                        'dt_copy_time')
         return pose
 
     def render_order(self):

@@ -68,7 +68,9 @@ extern "C" {
                                 layouts, a handle without them is unchanged);
                                 dt_bot_path, dt_set_bots, dt_render_bots
                                 (additive: lane-following duckiebots, the same
-                                way) */
+                                way); dt_step_many_time, dt_copy_time,
+                                dt_render_group (additive: each decision's
+                                step counter travels with its pose) */
 
 /* error codes */
 #define DT_OK 0
@@ -240,6 +242,17 @@ int dt_step_masked(dt_handle* h, const uint8_t* mask, const float* actions, doub
 int dt_step_many(dt_handle* h, int32_t k, const float* actions, double* reward,
                  double* reward_mod, uint8_t* done, float* obs, double* pose, void* stream);
 
+/* dt_step_many with each decision's time (dt_step_many is this call with time
+ * NULL):
+ *   time       device [k,n] u32: env e's Simulator step counter as decision d
+ *              left it -- what dt_get_state returns after d + 1 dt_step calls, 0
+ *              when decision d ended in an auto-reset -- i.e. the time dt_render
+ *              of that decision reads (dt_render_group's times[p] = time + n d)
+ *                                                                          nullable */
+int dt_step_many_time(dt_handle* h, int32_t k, const float* actions, double* reward,
+                      double* reward_mod, uint8_t* done, float* obs, double* pose, uint32_t* time,
+                      void* stream);
+
 /* Replaces: Simulator.get_lane_pos2(cur_pos, cur_angle) for every env (no step).
  * lanepos device [n,4] f64 (NaN if NotInLane); tile device [n] i32 (nullable). */
 int dt_lane_pos(dt_handle* h, double* lanepos, int32_t* tile, void* stream);
@@ -323,6 +336,25 @@ int dt_render2(dt_handle* h, const dt_render_io* io_a, const dt_render_io* io_b,
  * equals dt_render(io_a), dt_render(io_b), dt_render(io_c) in that order. */
 int dt_render3(dt_handle* h, const dt_render_io* io_a, const dt_render_io* io_b,
                const dt_render_io* io_c, void* stream);
+
+/* dt_render / dt_render2 / dt_render3 with each decision's time given: where a
+ * handle's walkers and bots stand in decision p's frame.
+ *   ios    host array of `parts` (1..3) dt_render_io pointers, earliest first
+ *   times  host array of `parts` device pointers, [n] u32 each (a row of
+ *          dt_step_many_time's time output, or a dt_copy_time snapshot); a NULL
+ *          entry, or times NULL (every entry NULL), means the handle's current
+ *          step_count, dt_render's rule
+ * parts = 1: dt_render(ios[0]) at that time (the snapshot render: pose and time
+ * of decision d while dt_step of d + 1 runs).  parts = 2 / 3: dt_render2 /
+ * dt_render3's conditions and outputs; on a handle with render walkers or bots
+ * it runs if and only if every times[p] is given, else DT_E_ARG (dt_last_error
+ * names dt_render_group).  A handle without them accepts and ignores times.
+ * Values past a table are defined: the walkers' closed form takes any t, the
+ * bots read row min(t, rows - 1).  DT_E_ARG also for parts outside 1..3, ios
+ * NULL or a NULL entry of it.  The time pointers are launch arguments: capture
+ * a graph that renders after they are fixed. */
+int dt_render_group(dt_handle* h, const dt_render_io* const* ios, const uint32_t* const* times,
+                    int32_t parts, void* stream);
 
 /* Draw the map's static objects into every later render of this handle (opt-in;
  * a new handle draws none, as before).  Upstream Simulator.render_obs draws
@@ -423,11 +455,12 @@ int dt_set_walkers(dt_handle* h, const double* recs, int32_t n);
  * it: q0 + float32(idx) * wx and q1 + float32(idx) * wz in float32, each
  * operation rounded (no fused multiply-add), idx as above from the handle's
  * step_count[e] -- also when dt_render_io.pose is set: the pose snapshot
- * carries no time, the time is the handle's current step_count.  The edge
- * vectors and squared lengths do not move.  dt_render2 / dt_render3 on a
- * handle with render walkers uploaded return DT_E_ARG: a grouped launch
- * renders several decisions from dt_step_many's pose output, which carries no
- * step counter.  A later dt_render_objects with another count switches the
+ * carries no time, the time is the handle's current step_count, unless
+ * dt_render_group gives the decision's own (dt_copy_time beside dt_copy_pose,
+ * or dt_step_many_time's time output).  The edge vectors and squared lengths
+ * do not move.  A grouped launch on a handle with render walkers goes through
+ * dt_render_group with every decision's time; dt_render2 / dt_render3 keep
+ * returning DT_E_ARG there (they take no time).  A later dt_render_objects with another count switches the
  * walkers off (n = 0).  Synchronous.  DT_E_ARG, with dt_last_error set and
  * nothing changed, for: n neither 0 nor that count, recs NULL with n > 0, a
  * non-finite value, K < 1 on a non-zero row, a W or K that is negative, not
@@ -531,8 +564,10 @@ int dt_set_bots(dt_handle* h, const double* recs, const int32_t* object_row, int
  *   n           0 switches them off
  * The render's phase 0c takes a bot's whole record from the table at
  * min(step_count[e], rows - 1) -- the handle's current step_count, also when
- * dt_render_io.pose is set.  dt_render2 / dt_render3 on a handle with render
- * bots return DT_E_ARG, as with render walkers.  A later dt_render_objects
+ * dt_render_io.pose is set, unless dt_render_group gives the decision's own
+ * time.  Grouped launches on a handle with render bots go through
+ * dt_render_group, as with render walkers; dt_render2 / dt_render3 keep
+ * returning DT_E_ARG.  A later dt_render_objects
  * with another count switches the bots off.  Synchronous.  Each upload
  * allocates its table and frees the one before, and the table's address is a
  * launch argument of dt_render: capture a graph that renders after this
@@ -553,6 +588,11 @@ int dt_render_order(dt_handle* h, uint32_t* launches, uint32_t* cost, int32_t* o
  * x, z, angle planes) on `stream`: the render of decision d can then read the
  * snapshot while dt_step of decision d + 1 runs on another stream. */
 int dt_copy_pose(dt_handle* h, double* pose, void* stream);
+
+/* dt_copy_pose's companion: enqueue a copy of every env's Simulator step
+ * counter into time (device [n] u32), the time dt_render_group draws that
+ * snapshot's walkers and bots at. */
+int dt_copy_time(dt_handle* h, uint32_t* time, void* stream);
 int dt_set_line_params(dt_handle* h, const dt_line_params* p);
 
 /* LineDetectorHSV on caller images (no environment; features/line_detector1.py
