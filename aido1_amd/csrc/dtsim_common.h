@@ -263,6 +263,9 @@ struct Geo {  // constants hoisted per launch
 // The rare exact paths are out-of-line calls: as inline code the compiler
 // speculates them (the division and sqrt are single IR operations) and every
 // lane would pay for them on every call.
+// On a 0.61 grid the one value within 60 ulps of an edge k <= 16 where the two
+// floors differ is one ulp below 9 * 0.61 (the reciprocal says 9, the division
+// 8): no shipped map is that wide, tests/test_gpu_step_edges.py builds one.
 static __device__ __noinline__ double floor_div_exact(double v, double ts) { return floor(v / ts); }
 
 __device__ inline double floor_div_ts(double v, const Geo& g) {

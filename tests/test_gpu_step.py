@@ -133,7 +133,8 @@ def test_step_parity_variants(gpu):
 
 def test_injected_edge_states(gpu):
     """Injected states: off-road start (invalid pose), wrapper cap boundary,
-    Simulator max_steps boundary, straight-line (Vl == Vr) branch."""
+    Simulator max_steps boundary, straight-line (Vl == Vr) branch.
+    (Poses on tile edges and bisection ties: tests/test_gpu_step_edges.py.)"""
     n = 256
     env, ob = make_pair(n, max_steps=1000)
     env.reset()
