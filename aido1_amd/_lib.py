@@ -186,6 +186,7 @@ def bind(L):
         'dt_render_group': (ctypes.c_int, [vp, vp, vp, i32, vp]),
         'dt_copy_time': (ctypes.c_int, [vp, vp, vp]),
         'dt_render_objects': (ctypes.c_int, [vp, vp, i32]),
+        'dt_render_camera': (ctypes.c_int, [vp, vp, i32]),
         'dt_set_walkers': (ctypes.c_int, [vp, vp, i32]),
         'dt_render_walkers': (ctypes.c_int, [vp, vp, i32]),
         'dt_bot_path': (ctypes.c_int, [vp, vp, vp, i32, i32, vp]),

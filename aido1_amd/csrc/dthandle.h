@@ -56,6 +56,9 @@ struct dt_handle {
   void* render_bot_col = nullptr;       // int32 [DT_MAX_RENDER_OBJECTS]: column or -1
   int32_t n_render_bots = 0, render_bot_rows = 0;
   std::vector<int32_t> render_bot_row;  // [n_render_bots] records of dt_render_objects
+  // dt_render_camera: the forward view's gather table (on: the kCam kernels run)
+  void* render_cam = nullptr;           // uint16 [120 * 160], allocated once
+  bool render_cam_on = false;
   std::string err;
 };
 

@@ -351,6 +351,10 @@ struct RenderArgs {
   const float4* bots;
   const int32_t* bot_col;
   uint32_t bot_rows, n_bots;
+  // dt_render_camera (the kCam kernels): the forward view's gather table, four
+  // 16-bit entries (a word of the frame) a uint2: the top-down pixel a pixel
+  // shows, or 0xFFFF for none
+  const uint2* cam;
 };
 
 // ---- fused render kernel ----------------------------------------------------------
@@ -377,6 +381,11 @@ struct RenderArgs {
 //       span's pixel centres against the rectangle and store PAL_RED over
 //       whatever lies below (a plain byte store: every object writes the
 //       same value)
+//   0d  (kCam: dt_render_camera) the forward camera's view of the raster: every
+//       word of the frame gathers its four bytes from the top-down image
+//       through the handle's table (PAL_FLOOR where a pixel sees nothing),
+//       held in registers across a barrier, then stored over the image.
+//       Nothing after this phase knows which view it works on
 //   1   every 16-pixel quad: neighbourhood uniformity of its 4 words;
 //       non-uniform words get a slot (the list)
 //   2a  listed words: SWAR 3-channel Sobel -> entry (mag | dir); the slot + 1
@@ -1394,8 +1403,49 @@ __device__ __forceinline__ void draw_objects(const RenderArgs& a, RenderLds& S, 
   __syncthreads();
 }
 
+// Phase 0d.  The image is complete (palette bytes, bits 0-2 only: the slot bits
+// come in phase 2a) and the union area is not used.  A lane's words (tid + k T)
+// are gathered into registers, the table's loads all issued first (8 bytes a
+// word, consecutive lanes consecutive: L2-resident, the same for every env);
+// after the barrier nobody reads the top-down image any more and the words go
+// back over it.  Ends with the barrier phase 1 needs.
+__device__ __forceinline__ void gather_camera(const RenderArgs& a, RenderLds& S) {
+  const int tid = opaque_tid();
+  constexpr int T = kRenderThreads, kPer = (NW + T - 1) / T;
+  const uint8_t* const pix = reinterpret_cast<const uint8_t*>(S.img);
+  uint2 t[kPer];
+#pragma unroll
+  for (int k = 0; k < kPer; ++k) {
+    const int w = tid + k * T;
+    t[k] = a.cam[w < NW ? w : NW - 1];
+  }
+  uint32_t out[kPer];
+#pragma unroll
+  for (int k = 0; k < kPer; ++k) {
+    const uint32_t idx[4] = {t[k].x & 0xFFFFu, t[k].x >> 16, t[k].y & 0xFFFFu, t[k].y >> 16};
+    uint32_t wd = 0u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      // an entry past the image is 0xFFFF (dt_render_camera refuses the
+      // others): sky, or ground the raster does not reach.  No read leaves
+      // the image whatever the table holds
+      const bool in = idx[i] < (uint32_t)NPIX;
+      const uint32_t b = pix[in ? idx[i] : 0u];
+      wd |= (in ? b : (uint32_t)PAL_FLOOR) << (8 * i);
+    }
+    out[k] = wd;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < kPer; ++k) {
+    const int w = tid + k * T;
+    if (w < NW) S.img[w] = out[k];
+  }
+  __syncthreads();
+}
+
 // One env of render_kernel.
-template <bool kIdx, bool kBigR, int kObj>
+template <bool kIdx, bool kBigR, int kObj, bool kCam>
 __device__ __forceinline__ void render_env(const RenderArgs& a, RenderLds& S, int e, int half,
                                            int vi
 #ifdef DTSIM_EARLY_MARKS
@@ -1556,6 +1606,7 @@ __device__ __forceinline__ void render_env(const RenderArgs& a, RenderLds& S, in
   }
   __syncthreads();
   if (kObj) draw_objects<kObj == 2>(a, S, V, e, half);
+  if (kCam) gather_camera(a, S);
   RENT(6);
   RENDER_STOP(2);
 
@@ -1667,9 +1718,10 @@ __device__ __forceinline__ void render_env(const RenderArgs& a, RenderLds& S, in
 #endif
 // kIdx: palette-byte frames (a.index) instead of grey floats; kBigR: a
 // dilation radius of 2-3; kObj: the object footprints are drawn (phase 0c).
+// kCam: the forward camera's view (phase 0d, dt_render_camera).
 // All are fixed for a launch: the host picks.
 // (kObj = 2: with dt_render_bots' table.)
-template <bool kIdx, bool kBigR, int kObj>
+template <bool kIdx, bool kBigR, int kObj, bool kCam>
 __global__ __launch_bounds__(kRenderThreads) __attribute__((amdgpu_waves_per_eu(DTSIM_RENDER_WPE))) void
 render_kernel(RenderArgs a) {
   __shared__ __attribute__((aligned(16))) RenderLds S;
@@ -1746,13 +1798,27 @@ render_kernel(RenderArgs a) {
       if (tid < kNCnt) S.cnt[tid] = 0;
       __syncthreads();
     }
-    render_env<kIdx, kBigR, kObj>(a, S, e, half0 + vi, vi
+    render_env<kIdx, kBigR, kObj, kCam>(a, S, e, half0 + vi, vi
 #ifdef DTSIM_EARLY_MARKS
                , mq
 #endif
     );
   }
   if (a.sched) sched_exit(a, S, e);
+}
+
+// the instantiation a launch runs (host)
+using RenderKernel = decltype(&render_kernel<false, false, 0, false>);
+template <bool kCam>
+RenderKernel pick_render(bool idx, bool big_r, bool bots, bool objs) {
+  if (bots)
+    return idx ? (big_r ? render_kernel<true, true, 2, kCam> : render_kernel<true, false, 2, kCam>)
+               : (big_r ? render_kernel<false, true, 2, kCam> : render_kernel<false, false, 2, kCam>);
+  if (objs)
+    return idx ? (big_r ? render_kernel<true, true, 1, kCam> : render_kernel<true, false, 1, kCam>)
+               : (big_r ? render_kernel<false, true, 1, kCam> : render_kernel<false, false, 1, kCam>);
+  return idx ? (big_r ? render_kernel<true, true, 0, kCam> : render_kernel<true, false, 0, kCam>)
+             : (big_r ? render_kernel<false, true, 0, kCam> : render_kernel<false, false, 0, kCam>);
 }
 
 // LineDetectorHSV on caller BGR images (one workgroup per image, <= 19200 px).
@@ -2132,6 +2198,9 @@ void dt_render_free(dt_handle* h) {
   if (h->render_bot_col) (void)hipFree(h->render_bot_col);
   h->render_bot_tab = h->render_bot_col = nullptr;
   h->n_render_bots = 0;
+  if (h->render_cam) (void)hipFree(h->render_cam);
+  h->render_cam = nullptr;
+  h->render_cam_on = false;
 }
 
 extern "C" {
@@ -2353,16 +2422,9 @@ static int render_launch(dt_handle* h, const dt_render_io* io, const dt_render_i
   a.bot_col = (const int32_t*)h->render_bot_col;
   a.bot_rows = (uint32_t)h->render_bot_rows;
   a.n_bots = (uint32_t)h->n_render_bots;
-  decltype(&render_kernel<false, false, 0>) kern;
-  if (bots)
-    kern = a.index ? (big_r ? render_kernel<true, true, 2> : render_kernel<true, false, 2>)
-                   : (big_r ? render_kernel<false, true, 2> : render_kernel<false, false, 2>);
-  else if (a.n_objs > 0)
-    kern = a.index ? (big_r ? render_kernel<true, true, 1> : render_kernel<true, false, 1>)
-                   : (big_r ? render_kernel<false, true, 1> : render_kernel<false, false, 1>);
-  else
-    kern = a.index ? (big_r ? render_kernel<true, true, 0> : render_kernel<true, false, 0>)
-                   : (big_r ? render_kernel<false, true, 0> : render_kernel<false, false, 0>);
+  a.cam = h->render_cam_on ? (const uint2*)h->render_cam : nullptr;
+  const RenderKernel kern = a.cam ? pick_render<true>(a.index != nullptr, big_r, bots, a.n_objs > 0)
+                                  : pick_render<false>(a.index != nullptr, big_r, bots, a.n_objs > 0);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, a);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -2540,6 +2602,34 @@ int dt_render_bots(dt_handle* h, const float* recs, const int32_t* render_row, i
   h->render_bot_rows = rows;
   h->n_render_bots = n;
   h->render_bot_row.assign(render_row, render_row + n);
+  return DT_OK;
+}
+
+int dt_render_camera(dt_handle* h, const uint16_t* table, int32_t n) {
+  if (!h) return DT_E_ARG;
+  if (!table && n == 0) {   // off: later launches are the top-down kernels again
+    h->render_cam_on = false;
+    return DT_OK;
+  }
+  if (!table || n != NPIX) {
+    h->err = "dt_render_camera: a table of 19200 entries, or NULL and 0 to switch the camera off";
+    return DT_E_ARG;
+  }
+  // the memory-safety guard: an entry is a pixel of the raster or 0xFFFF
+  for (int i = 0; i < NPIX; ++i)
+    if (table[i] >= NPIX && table[i] != 0xFFFFu) {
+      h->err = "dt_render_camera: entry " + std::to_string(i) + " (" + std::to_string(table[i]) +
+               ") is neither a pixel (0..19199) nor 65535";
+      return DT_E_ARG;
+    }
+  DevGuard dg(h->device);
+  // launches in flight read the table: wait for them (synchronous, as
+  // dt_render_objects); one buffer for the handle's life, so a launch captured
+  // into a graph keeps a valid pointer and reads whatever was uploaded last
+  HIP_OR_FAIL(h, hipDeviceSynchronize());
+  if (!h->render_cam) HIP_OR_FAIL(h, hipMalloc(&h->render_cam, NPIX * sizeof(uint16_t)));
+  HIP_OR_FAIL(h, hipMemcpy(h->render_cam, table, NPIX * sizeof(uint16_t), hipMemcpyHostToDevice));
+  h->render_cam_on = true;
   return DT_OK;
 }
 

@@ -68,7 +68,7 @@ class GpuBatch:
 
     def __init__(self, n_envs, map_name='loop_empty', seed=0, device=None, env_id_base=0,
                  max_steps=500001, accept_start_angle_deg=4, frame_skip=1, frame_rate=30,
-                 draw_objects=False, lane_bots=False, bot_rows=None):
+                 draw_objects=False, lane_bots=False, bot_rows=None, camera=None):
         import torch
         from aido1_amd.config import EnvConfig
         from aido1_amd.render import RenderOutput
@@ -81,7 +81,8 @@ class GpuBatch:
         self.torch = torch
         self.n = n_envs
         self.env = VecEnv(n_envs, seed=seed, device=device, config=cfg, env_id_base=env_id_base,
-                          draw_objects=draw_objects, lane_bots=lane_bots, bot_rows=bot_rows)
+                          draw_objects=draw_objects, lane_bots=lane_bots, bot_rows=bot_rows,
+                          camera=camera)
         self.dev = self.env.device
         self.out = StepOutput(n_envs, self.dev)
         self.render = RenderOutput(n_envs, self.dev, slots=1, rgb=True, masks=False)
@@ -283,10 +284,13 @@ def main(argv=None):
     p.add_argument('--bot-rows', type=int, default=None,
                    help='rows of the bots\' path table (Simulator steps an episode can reach; '
                         'needed with --lane-bots: the server\'s max_steps is over the cap)')
+    p.add_argument('--camera', choices=['ego'], default=None,
+                   help='observations from the forward camera (a perspective warp of the '
+                        'top-down raster) instead of the raster itself')
     a = p.parse_args(argv)
     srv = EnvServer(GpuBatch(a.n_envs, map_name=a.map, seed=a.seed, device=a.device,
                              draw_objects=a.draw_objects, lane_bots=a.lane_bots,
-                             bot_rows=a.bot_rows),
+                             bot_rows=a.bot_rows, camera=a.camera),
                     host=a.host, port_start=a.port).start()
     print('serving %d envs on %s:%d-%d' % (a.n_envs, a.host, a.port, a.port + a.n_envs - 1),
           flush=True)

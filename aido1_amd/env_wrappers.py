@@ -55,11 +55,11 @@ def map_tanh_in_place(action):
 class EnvironmentWrapper:
     def __init__(self, config, n_envs=4096, device=None, seed=123, map_name='loop_empty',
                  obs='render', env_id_base=0, draw_objects=False, lane_bots=False,
-                 **env_overrides):
+                 camera=None, **env_overrides):
         self.config = config
         ec = EnvConfig.from_reference_config(config, map_name=map_name, **env_overrides)
         self.env = VecEnv(n_envs, seed=seed, device=device, config=ec, env_id_base=env_id_base,
-                          draw_objects=draw_objects, lane_bots=lane_bots)
+                          draw_objects=draw_objects, lane_bots=lane_bots, camera=camera)
         self.n = n_envs
         self.obs_mode = obs
         self.render = RenderOutput(n_envs, self.env.device, slots=3) if obs == 'render' else None

@@ -64,7 +64,7 @@ class ActorRollout:
     def __init__(self, config, n_envs=4096, maps=('small_loop', 'zigzag'), device=0, seed=1234,
                  env_id_base=0, actor=None, dtype=torch.float32, masks=True,
                  actor_mode='reference', fused_explore=True, n_exploit=None, guard=None,
-                 frames='index', draw_objects=False, lane_bots=False):
+                 frames='index', draw_objects=False, lane_bots=False, camera=None):
         self.config = config
         self.guard = guard      # non-finite guard (guard.py): actor outputs, rewards
         self.device = torch.device('cuda', device)
@@ -86,7 +86,7 @@ class ActorRollout:
         for m, sz in zip(maps, sizes):
             ec = EnvConfig.from_reference_config(config, map_name=m)
             env = VecEnv(sz, seed=seed, device=device, config=ec, env_id_base=env_id_base + off,
-                         draw_objects=draw_objects, lane_bots=lane_bots)
+                         draw_objects=draw_objects, lane_bots=lane_bots, camera=camera)
             sl = slice(off, off + sz)
             out = StepOutput(sz, self.device, lanepos=False, tile=False)
             out.reward, out.reward_mod, out.done = self.reward[sl], self.reward_mod[sl], \

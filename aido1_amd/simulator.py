@@ -18,10 +18,18 @@ The observation is the build's 120x160 ego-centric top-down raster (the
 reference's OpenGL 640x480 camera frame does not exist here; the reference's
 wrappers resize every frame to 120x160 anyway, ResizeWrapper /
 PreliminaryTransformer, so camera_width/height are accepted and ignored).
+With ``camera='ego'`` (or a camera.EgoCamera) the observation is the forward
+camera's view of the ground instead: a perspective warp of that raster
+(aido1_amd/camera.py), 120x160 whatever camera_width/height say, and
+``distortion=True`` is then honoured ('ego' with the radial lens model; an
+EgoCamera carries its own switch).  Without ``camera`` distortion stays
+ignored.  The view is build-defined: 1 cm ground resolution, nothing beyond
+1.2 m, unpinned against upstream's frame.
 """
 import numpy as np
 import torch
 
+from aido1_amd.camera import resolve as resolve_camera
 from aido1_amd.config import EnvConfig, REWARD_INVALID_POSE  # noqa: F401
 from aido1_amd.render import H, W, RenderOutput
 
@@ -69,7 +77,8 @@ class Simulator:
                  camera_width=640, camera_height=480, accept_start_angle_deg=60,
                  full_transparency=False, distortion=False, frame_skip=1, draw_curve=False,
                  draw_bbox=False, robot_speed=None, frame_rate=30, device=None, env_id=0,
-                 draw_objects=False, lane_bots=False, bot_rows=None, **unsupported):
+                 draw_objects=False, lane_bots=False, bot_rows=None, camera=None,
+                 **unsupported):
         if domain_rand:
             raise NotImplementedError('domain randomisation is not on the hot path '
                                       '(launch_env passes domain_rand=0, env.py:11)')
@@ -85,7 +94,8 @@ class Simulator:
         self.config = cfg
         self._seed = 0 if seed is None else int(seed)
         self._env = VecEnv(1, seed=self._seed, device=device, config=cfg, env_id_base=env_id,
-                           draw_objects=draw_objects, lane_bots=lane_bots, bot_rows=bot_rows)
+                           draw_objects=draw_objects, lane_bots=lane_bots, bot_rows=bot_rows,
+                           camera=resolve_camera(camera, distortion))
         self._dev = self._env.device
         self._out = RenderOutput(1, self._dev, slots=1, rgb=True, masks=False)
         self._act = torch.zeros(1, 2, dtype=torch.float32, device=self._dev)

@@ -80,7 +80,7 @@ class TrainLoop:
                  actor_mode='reference', masks=False, graph=True, overlap=False, n_exploit=None,
                  save_dir=None, log_dir=None, poll_every=0, check_every=0, frames='index',
                  importance_weights=False, beta_decay=None, draw_objects=False,
-                 lane_bots=False):
+                 lane_bots=False, camera=None):
         t = config['training']
         if importance_weights and not prioritized:
             raise ValueError('importance_weights needs prioritized=True (the weights are the '
@@ -106,7 +106,8 @@ class TrainLoop:
                                     env_id_base=env_id_base, actor=self.trainer.actor,
                                     dtype=actor_dtype, masks=masks, actor_mode=actor_mode,
                                     n_exploit=n_exploit, guard=self.guard, frames=frames,
-                                    draw_objects=draw_objects, lane_bots=lane_bots)
+                                    draw_objects=draw_objects, lane_bots=lane_bots,
+                                    camera=camera)
         self.rollout.load_exploit_actor(self.trainer.target_actor)
         size = int(buffer_size or t['buffer_size'])
         gen = torch.Generator(device=self.device)

@@ -74,12 +74,17 @@ class VecEnv:
         the most a wrapped episode can reach.  Past the last row a bot stands
         still.
 
+      camera: None (the top-down raster, as always), 'ego' (camera.EgoCamera's
+        defaults) or an EgoCamera: the observation is the robot's forward
+        camera's view of the ground, a perspective warp of the raster
+        (dt_render_camera; see set_camera).
+
     A map with walkers always has them in collision and the reward
     (dt_set_walkers), whatever draw_objects says.
     """
 
     def __init__(self, n_envs, map_name=None, seed=123, device=None, config=None,
-                 env_id_base=0, draw_objects=False, lane_bots=False, bot_rows=None):
+                 env_id_base=0, draw_objects=False, lane_bots=False, bot_rows=None, camera=None):
         self.config = config or EnvConfig()
         if map_name is not None:
             self.config = self.config.replace(map_name=map_name)
@@ -147,6 +152,9 @@ class VecEnv:
                 rc = self._L.dt_render_bots(self._h, rec.ctypes.data_as(ctypes.c_void_p),
                                             row.ctypes.data_as(ctypes.c_void_p), len(rec), nb)
                 _lib.check(self._L, self._h, rc, 'dt_render_bots')
+        self.camera = None
+        if camera is not None:
+            self.set_camera(camera)
         self.seed(seed)
         self.out = StepOutput(self.n, self.device)
         self._reset_obs = torch.zeros(self.n, 2, dtype=torch.float32, device=self.device)
@@ -364,9 +372,9 @@ class VecEnv:
 
     # ---- observation path (config 3) ----------------------------------------------------
     def render_into(self, out, fresh=None, pose=None, list_cap=0, time=None):
-        """Top-down raster + grey + line masks of every env's current pose (or of a
-        copy_pose snapshot, with its time) into a RenderOutput (see
-        aido1_amd/render.py)."""
+        """Top-down raster (with a camera set: its forward view, set_camera) +
+        grey + line masks of every env's current pose (or of a copy_pose
+        snapshot, with its time) into a RenderOutput (see aido1_amd/render.py)."""
         from aido1_amd.render import render_into
         return render_into(self, out, fresh, pose, list_cap, time)
 
@@ -400,6 +408,32 @@ class VecEnv:
                                             order.ctypes.data_as(ctypes.c_void_p)),
                     'dt_render_order')
         return launches.value, cost, order
+
+    def set_camera(self, camera):
+        """The view every later render of this env draws: None, the top-down
+        raster; 'ego' or a camera.EgoCamera, the forward camera's view of it
+        (every frame pixel shows one raster pixel, or black for sky and for
+        ground past the raster's 1.2 m; objects, walkers and bots included;
+        the ring, the masks and rgb are all the forward frame's).  A raw
+        uint16 [120, 160] gather table (camera.check_table) is taken too.
+        Build-defined: 1 cm ground resolution, so blocky near the camera, and
+        unpinned against upstream's OpenGL frame.  Synchronous.  A captured
+        graph follows a replaced table, but switching the camera on or off
+        picks other kernels: capture again after it."""
+        from aido1_amd import camera as C
+        if camera is None:
+            self._check(self._L.dt_render_camera(self._h, _NULL, 0), 'dt_render_camera')
+            self.camera = None
+            return
+        if isinstance(camera, np.ndarray):
+            table = C.check_table(camera)
+        else:
+            camera = C.resolve(camera)
+            table = camera.table()
+        table = np.ascontiguousarray(table)
+        self._check(self._L.dt_render_camera(self._h, table.ctypes.data_as(ctypes.c_void_p),
+                                             table.size), 'dt_render_camera')
+        self.camera = camera
 
     def set_line_params(self, params):
         self._check(self._L.dt_set_line_params(self._h, ctypes.byref(params)),

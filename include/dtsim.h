@@ -388,6 +388,35 @@ int dt_render_group(dt_handle* h, const dt_render_io* const* ios, const uint32_t
 #define DT_MAX_RENDER_OBJECTS 256
 int dt_render_objects(dt_handle* h, const float* recs, int32_t n);
 
+/* The forward-camera observation (opt-in; a new handle renders the top-down
+ * raster, as before).  Replaces what the reference trains on, the robot's
+ * forward camera (Simulator(camera_width=640, camera_height=480,
+ * distortion=True), duckietown_rl/env.py:12-16, resized to 120x160), with a
+ * perspective warp of this build's raster: the camera is rigid on the robot and
+ * the ground is flat, so each pixel of the forward view shows one fixed pixel
+ * of the top-down raster or nothing (sky, or ground past the raster's 1.2 m).
+ *   table  host [120 * 160] u16: for the frame's pixel (r, c), entry r * 160 + c
+ *          is the top-down pixel rs * 160 + cs it shows, or 0xFFFF for none
+ *          (drawn as the palette's floor byte, black).  Pinhole, tilt, field of
+ *          view and lens distortion are only different tables
+ *          (aido1_amd/camera.py EgoCamera.table)
+ *   n      19200 with a table switches the camera on; NULL and 0 switch it off
+ * Every later render of the handle (dt_render, dt_render2, dt_render3,
+ * dt_render_group; every output format, dilation size and object set) first
+ * draws the top-down raster, objects, walkers and bots included, then gathers
+ * the frame through the table (render_kernel's phase 0d), and the grey or index
+ * frame, the masks, Canny's edges and the rgb output are the forward frame's.
+ * The view is build-defined, like the raster it is made from: 1 cm ground
+ * resolution (blocky near the camera), nothing beyond 1.2 m, and parity with
+ * upstream's OpenGL frame is not pinned.
+ * Synchronous: waits for the device, then uploads into one allocation the
+ * handle keeps for its life, so a captured launch of a handle whose camera is
+ * on follows a table uploaded later.  Switching the camera on or off selects
+ * other kernels: capture again after it.  DT_E_ARG, with dt_last_error set and
+ * nothing changed or copied, for any other (table, n) and for an entry in
+ * 19200..65534. */
+int dt_render_camera(dt_handle* h, const uint16_t* table, int32_t n);
+
 /* ---- walkers: moving objects (upstream DuckieObj, the walking duckie) ------
  * Recalled from upstream, gym-duckietown being absent: parity is unpinned, as
  * for the static objects.  Upstream's DuckieObj.step without domain
