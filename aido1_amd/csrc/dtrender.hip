@@ -497,6 +497,9 @@ __device__ inline int sobel_swar(uint32_t a00, uint32_t a01, uint32_t a02, uint3
   return best;
 }
 
+// c ? a : b on values (one v_cndmask)
+__device__ __forceinline__ uint32_t sel32(bool c, uint32_t a, uint32_t b) { return c ? a : b; }
+
 // b (< 256) in all four bytes: one v_perm, not a 32-bit multiply
 __device__ inline uint32_t splat_byte(uint32_t b) { return __builtin_amdgcn_perm(0u, b, 0u); }
 
@@ -687,8 +690,11 @@ __device__ inline void draw_line_part(lds_u32* img, int x0, int y0, int x1, int 
 }
 
 __device__ inline int proj(float v) {  // round-to-nearest pixel, clamped far off-screen
-  v = floorf(v + 0.5f);
-  v = v < -100000.0f ? -100000.0f : (v > 100000.0f ? 100000.0f : v);
+  // the clamp as one v_med3_f32: the same value for every finite or infinite
+  // v.  A NaN (only from a NaN pose) gives -100000, the median instruction's
+  // minimum of the other two, where the compares gave 0: such a segment is
+  // now culled off-screen instead of collapsing onto pixel (0, 0)
+  v = __builtin_amdgcn_fmed3f(floorf(v + 0.5f), -100000.0f, 100000.0f);
   return (int)v;
 }
 
@@ -975,17 +981,19 @@ __device__ __forceinline__ void canny(const RenderArgs& a, RenderLds& S, int e,
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int m = (int)(vv[i] & WK_MAG);
-        const int dir = (int)(vv[i] >> WK_DIR_SHIFT) & 3;
         // dir 0: (0,-1)/(0,+1); 1: (-1,0)/(+1,0); 2: (-1,-1)/(+1,+1); 3: (-1,+1)/(+1,-1).
-        // Selected with all-ones masks, not a select chain: the chain becomes an
-        // indexed read of M, which the compiler then keeps in scratch memory.
-        const uint32_t d0 = 0u - (uint32_t)(dir == 0), d1 = 0u - (uint32_t)(dir == 1),
-                       d2 = 0u - (uint32_t)(dir == 2), d3 = 0u - (uint32_t)(dir == 3);
-        const int n1 = (int)((d0 & M[1][i]) | (d1 & M[0][i + 1]) | (d2 & M[0][i]) |
-                             (d3 & M[0][i + 2]));
-        const int n2 = (int)((d0 & M[1][i + 2]) | (d1 & M[2][i + 1]) | (d2 & M[2][i + 2]) |
-                             (d3 & M[2][i]));
-        const bool keep = act && m > L.canny_lo && m > n1 && (dir >= 2 ? m > n2 : m >= n2);
+        // Selected on the direction's two bits, two levels of v_cndmask with
+        // the bit tests shared by both neighbours.  Through sel32, whose operands
+        // are values read before the choice: a ?: on two elements of M reads
+        // M through a chosen address, an indexed read that keeps M in scratch
+        // memory (as a chain on dir == k did).
+        const bool b0 = (vv[i] & (1u << WK_DIR_SHIFT)) != 0u;
+        const bool b1 = (vv[i] & (2u << WK_DIR_SHIFT)) != 0u;
+        const uint32_t n1a = sel32(b0, M[0][i + 1], M[1][i]), n1b = sel32(b0, M[0][i + 2], M[0][i]);
+        const uint32_t n2a = sel32(b0, M[2][i + 1], M[1][i + 2]),
+                       n2b = sel32(b0, M[2][i], M[2][i + 2]);
+        const int n1 = (int)sel32(b1, n1b, n1a), n2 = (int)sel32(b1, n2b, n2a);
+        const bool keep = act && m > L.canny_lo && m > n1 && (b1 ? m > n2 : m >= n2);
         const bool strong = m > L.canny_hi;
         setb[i] = keep ? (strong ? (uint32_t)(WK_CAND | WK_EDGE) : (uint32_t)WK_CAND) : 0u;
         want[4 * u + i] = keep && !strong;
@@ -1621,64 +1629,93 @@ __device__ __forceinline__ void render_env(const RenderArgs& a, RenderLds& S, in
   constexpr int kQuadPer = (NQ + T - 1) / T;  // quads per lane (3 at 512 threads)
   if (mbase) {
     bool non[4 * kQuadPer];
-#pragma unroll
-    for (int k = 0; k < kQuadPer; ++k) {
-      // straight-line over the lane's quads (clamped, flagged): their LDS
-      // reads and tests interleave
+    // one round: the lane's quad tid + k T (clamped, flagged).  A word's 3 x 6
+    // pixels are one colour iff the three rows agree on them and row 1's five
+    // adjacent pairs are equal, so the quad's six words a row (the side words
+    // included) are compared once, by pairs: V[j] the rows' disagreement on
+    // word j, A[j] that or a pixel of row 1 differing from its right neighbour
+    // (v_alignbyte: the next word's byte 0 beside byte 3).  Word j of the quad
+    // (j + 1 of the six) then reads pixels 4j .. 4j + 3 and their four right
+    // pairs in A[j + 1], pixel 4j - 1 and its pair in A[j]'s top byte, pixel
+    // 4j + 4 in V[j + 2]'s low byte.
+    const auto round = [&](int k) {
       const int qq = tid + k * T;
       const bool act = qq < NQ;
       const int q = act ? qq : NQ - 1;
       const int r = q / QPR, cw0 = 4 * (q - r * QPR);
-      uint32_t m[3][4], lw[3], rw[3];
+      uint32_t m[3][6];
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
         int rr = r - 1 + i;
         rr = rr < 0 ? 0 : (rr > H - 1 ? H - 1 : rr);
         const uint32_t* row = S.img + rr * WPR;
         const uint4 v = *reinterpret_cast<const uint4*>(row + cw0);
-        m[i][0] = v.x;
-        m[i][1] = v.y;
-        m[i][2] = v.z;
-        m[i][3] = v.w;
+        m[i][1] = v.x;
+        m[i][2] = v.y;
+        m[i][3] = v.z;
+        m[i][4] = v.w;
         // side words at the image edge clamp to the quad's own edge word:
-        // BORDER_REPLICATE repeats the edge pixel, already compared
-        lw[i] = row[cw0 > 0 ? cw0 - 1 : cw0];
-        rw[i] = row[cw0 + 4 < WPR ? cw0 + 4 : cw0 + 3];
+        // BORDER_REPLICATE repeats the edge pixel, and the byte the clamped
+        // word adds pairs two pixels of that one word, which its own test covers
+        m[i][0] = row[cw0 > 0 ? cw0 - 1 : cw0];
+        m[i][5] = row[cw0 + 4 < WPR ? cw0 + 4 : cw0 + 3];
       }
+      uint32_t Vd[6], Ad[5];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) Vd[j] = (m[0][j] ^ m[1][j]) | (m[1][j] ^ m[2][j]);
+#pragma unroll
+      for (int j = 0; j < 5; ++j)
+        Ad[j] = Vd[j] | (m[1][j] ^ __builtin_amdgcn_alignbyte(m[1][j + 1], m[1][j], 1u));
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const uint32_t rep = splat_byte(m[1][j] & 255u);
-        // per row the word's 6-pixel span as two byte-shifted words (v_alignbyte):
-        // pixels 4j-1 .. 4j+2 and 4j+1 .. 4j+4, each compared with the splat
-        uint32_t diff = 0u;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-          const uint32_t lft = j > 0 ? m[i][j - 1] : lw[i], rgt = j < 3 ? m[i][j + 1] : rw[i];
-          diff |= (__builtin_amdgcn_alignbyte(m[i][j], lft, 3u) ^ rep) |
-                  (__builtin_amdgcn_alignbyte(rgt, m[i][j], 1u) ^ rep);
-        }
+        const uint32_t diff = Ad[j + 1] | (Ad[j] & 0xFF000000u) | (Vd[j + 2] & 0xFFu);
         non[4 * k + j] = act && diff != 0u;
+      }
+    };
+    // the rounds every wave has a quad in are one straight-line block (their
+    // LDS reads and tests interleave); a later round runs only in the waves
+    // whose first lane still has one (wave-uniform: round 2 of 1200 quads at
+    // 512 threads is waves 0-2).  Register allocation decides two details
+    // (compiled both ways, all 24 instantiations): the guarded round goes
+    // first, so its flags are scalars before the block takes its registers
+    // (behind the block up to 7 VGPRs spill in the radius 2-3 kernels), and
+    // `act` stays the plain test in the full rounds too (folded to true there,
+    // the kernels go to 63-64 VGPRs and ten of them spill one).
+#pragma unroll
+    for (int k = kQuadPer - 1; k >= 0; --k) {
+      if ((k + 1) * T <= NQ) {
+        round(k);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) non[4 * k + j] = false;
+        if ((tid & ~63) + k * T < NQ) round(k);
       }
     }
     int slot[4 * kQuadPer];
 #pragma unroll
     for (int k = 0; k < 4 * kQuadPer; ++k) slot[k] = 0;
     wave_slotsN<4 * kQuadPer>(&C[kNList], non, slot);
-    uint16_t* gl = a.spill + (size_t)e * kSpillHalves + 4 * NW;
+    // the wave's slots end at lane 63's last one (0 when the wave listed
+    // nothing): below the cap, the common case, every store is an LDS store
+    // and no item tests its slot; a wave that reaches the cap tests each
+    // (non[] is false for a quad past the image)
+    const int wave_end = __builtin_amdgcn_readlane(
+        slot[4 * kQuadPer - 1] + (non[4 * kQuadPer - 1] ? 1 : 0), 63);
+    if (wave_end <= a.list_cap) {
 #pragma unroll
-    for (int k = 0; k < kQuadPer; ++k) {
-      const int q = tid + k * T;
-      if (q < NQ) {
+      for (int k = 0; k < 4 * kQuadPer; ++k)
+        if (non[k]) S.u.w.list[slot[k]] = (uint16_t)(4 * (tid + (k >> 2) * T) + (k & 3));
+    } else {
+      uint16_t* gl = a.spill + (size_t)e * kSpillHalves + 4 * NW;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int w = 4 * q + j;
-          const int sj = slot[4 * k + j];
-          if (non[4 * k + j]) {
-            if (sj < a.list_cap)
-              S.u.w.list[sj] = (uint16_t)w;
-            else
-              gl[sj] = (uint16_t)w;
-          }
+      for (int k = 0; k < 4 * kQuadPer; ++k) {
+        const int w = 4 * (tid + (k >> 2) * T) + (k & 3);
+        const int sj = slot[k];
+        if (non[k]) {
+          if (sj < a.list_cap)
+            S.u.w.list[sj] = (uint16_t)w;
+          else
+            gl[sj] = (uint16_t)w;
         }
       }
     }

@@ -1,6 +1,7 @@
 """tools/render_phase_valu.sh helpers: `build` the phase-stop diagnostic
-libraries (CPU, here); `report` the per-dispatch instruction counts of
-render_kernel per build and their differences (the phases' shares)."""
+libraries (CPU, here); `report [suffix]` the per-dispatch instruction counts
+of render_kernel per build (of the set measured under that suffix) and their
+differences (the phases' shares)."""
 import csv
 import glob
 import os
@@ -21,9 +22,10 @@ def build():
         print('built', k)
 
 
-def report():
+def report(sfx=''):
     prev = None
-    for k in STOPS:
+    for stop in STOPS:
+        k = stop + sfx
         acc = {}
         for f in glob.glob('gpurun_out/rstop_%s/**/*counter_collection.csv' % k, recursive=True):
             for r in csv.DictReader(open(f)):
@@ -34,7 +36,7 @@ def report():
             continue
         m = {c: sum(v) / len(v) for c, v in acc.items()}
         waves = m.get('SQ_WAVES', 1.0)
-        line = '%-34s' % NAMES[k]
+        line = '%-34s' % NAMES[stop]
         for c in ('SQ_INSTS_VALU', 'SQ_INSTS_LDS', 'SQ_INSTS_SALU'):
             per = m.get(c, 0.0) / waves
             d = per - (prev[c] if prev else 0.0)
@@ -44,4 +46,4 @@ def report():
 
 
 if __name__ == '__main__':
-    {'build': build, 'report': report}[sys.argv[1]]()
+    {'build': build, 'report': report}[sys.argv[1]](*sys.argv[2:3])
