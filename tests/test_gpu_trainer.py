@@ -5,7 +5,9 @@ The update is compared with the reference's own DDPGTrainer.update
 convolutions (MIOpen) sum in a different order than CPU ones, so losses and
 TD errors agree to ~1e-5 relative; parameters after three Adam steps agree to
 rtol 1e-3 / atol 1e-3 (Adam's first steps move each weight by ~lr * sign(g),
-so a gradient within rounding noise of zero may step the other way)."""
+so a gradient within rounding noise of zero may step the other way).
+Adam hides a gradient's magnitude: tests/test_gpu_update_grads.py holds every
+gradient of the eager GPU stages to a float64 restatement with SGD."""
 import pytest
 import torch
 

@@ -10,7 +10,9 @@ sign follows rounding noise; one-ulp differences (e.g. torch's capturable vs
 plain Adam, tools/graph_probe.py) grow to percent-level loss differences by
 the third update.  So: float64 pins all three updates tightly; float32 pins
 the first update tightly and bounds the rest.  CPU here;
-tests/test_gpu_trainer.py repeats the float32 check on the GPU."""
+tests/test_gpu_trainer.py repeats the float32 check on the GPU.  Gradient
+magnitudes, which Adam's sign-like first step hides, are pinned by
+tests/test_update_ref.py (CPU) and tests/test_gpu_update_grads.py (GPU)."""
 import copy
 import sys
 
