@@ -317,6 +317,10 @@ def bind(L):
         'dt_explore': (ctypes.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                       ctypes.POINTER(DtExploreParams), vp, vp]),
         'dt_explore_done': (ctypes.c_int, [i32, vp, vp, vp, vp, i32, vp]),
+        'dt_explore_gauss': (ctypes.c_int, [i32, i32, vp, vp, vp, f64, f64, f64, vp, vp]),
+        'dt_substep_account': (ctypes.c_int, [i32, i32, vp, vp, vp, vp, vp, vp]),
+        'dt_decision_account': (ctypes.c_int, [i32, i32, vp, vp, vp, vp, vp, vp]),
+        'dt_stack_take': (ctypes.c_int, [vp, i32, i32, i32, ctypes.POINTER(i32), vp, vp, vp]),
         'dt_episode_account': (ctypes.c_int, [i32, i32, vp, vp, vp,
                                               ctypes.POINTER(DtEpisodeState), vp]),
         'dt_refresh_copy': (ctypes.c_int, [i32, vp, i64, vp]),

@@ -779,13 +779,22 @@ class FusedActor(nn.Module):
     def _convs_pair(self, other, x, order, n0):
         return self._convs(x, order, other, n0)
 
-    _HEAD_CODES = {'none': 0, 'tanh': 1, 'sigmoid': 2}
+    _HEAD_CODES = {'none': 0, 'tanh': 1, 'sigmoid': 2, 'sigmoid_tanh': 3}
+
+    def _head_code(self):
+        """The kernels' code of this actor's head (include/dtactor.h), None
+        where only the torch ops compute it: ActorCNN's sigmoid | tanh is
+        code 3 at max_action 1, the reference's value (train-ddpg-cnn.py:57);
+        any other max_action scales output 0 and stays on the torch path."""
+        if self.head == 'sigmoid_tanh' and self.max_action != 1.0:
+            return None
+        return self._HEAD_CODES.get(self.head)
 
     def _head_fusable(self, other=None):
         """The actors' fp16 heads fit one dt_actor_head launch."""
         nets = [self] if other is None else [self, other]
         return all(a.dtype == torch.float16 and a.w2.is_cuda and a.w2.shape[0] == 2 and
-                   a.head == self.head and a.head in self._HEAD_CODES and
+                   a.head == self.head and a._head_code() is not None and
                    a.w1.shape == self.w1.shape and a.w1.shape[0] % 8 == 0 for a in nets)
 
     def _head_x3_ok(self, x, other=None):
@@ -793,7 +802,7 @@ class FusedActor(nn.Module):
         nets = [self] if other is None else [self, other]
         return (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and
                 tuple(x.shape[1:]) == (FLAT,) and
-                all(hasattr(a, 'w1x') and a.head == self.head and a.head in self._HEAD_CODES and
+                all(hasattr(a, 'w1x') and a.head == self.head and a._head_code() is not None and
                     tuple(a.w2.shape) == (2, 512) for a in nets))
 
     def _head_path(self, flat, other=None):
@@ -868,7 +877,7 @@ class FusedActor(nn.Module):
         _lib.call(
             'dt_actor_head',
             n, n0, k, h.data_ptr(), k, self.w2.data_ptr(), self.b2.data_ptr(), o.w2.data_ptr(),
-            o.b2.data_ptr(), self._HEAD_CODES[self.head], 0.01, out.data_ptr(),
+            o.b2.data_ptr(), self._head_code(), 0.01, out.data_ptr(),
             ctypes.c_void_p(torch.cuda.current_stream(flat.device).cuda_stream))
 
     def _drop_seed(self, p):
@@ -901,7 +910,7 @@ class FusedActor(nn.Module):
             entry, n, n0, FLAT, flat.data_ptr(), float(p), self._drop_seed(p),
             getattr(self, w1).data_ptr(), self.b1.data_ptr(), self.w2.data_ptr(),
             self.b2.data_ptr(), getattr(o, w1).data_ptr(), o.b1.data_ptr(), o.w2.data_ptr(),
-            o.b2.data_ptr(), self._HEAD_CODES[self.head], 0.01,
+            o.b2.data_ptr(), self._head_code(), 0.01,
             self._head_work(n, flat.device).data_ptr(), out.data_ptr(),
             ctypes.c_void_p(torch.cuda.current_stream(flat.device).cuda_stream))
 

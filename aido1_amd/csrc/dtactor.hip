@@ -8,6 +8,7 @@
 #include <cstdint>
 
 #include "../../include/dtactor.h"
+#include "dtrender.h"   // dr::kPalGray: the grey levels of palette-index frames
 
 namespace {
 
@@ -296,6 +297,159 @@ extern "C" int dt_explore_done(int32_t n, const uint8_t* done, double* ou_x, int
   return hipGetLastError() == hipSuccess ? DT_OK : DT_E_HIP;
 }
 
+// ---- the batched train-ddpg-cnn.py decision (aido1_amd/cnn_rollout.py) --------------------
+// dt_explore_gauss, dt_substep_account, dt_decision_account: one lane an env,
+// every operation the one (and in the order) cnn_rollout.SubstepBook performs
+// with torch, so the two agree bit for bit.  dt_stack_take: the masked gather
+// of the 3-slot ring into a float32 stack.
+namespace {
+
+__global__ void __launch_bounds__(256)
+explore_gauss_kernel(int n, int n_warm, const float* __restrict__ actor_out,
+                     const double* __restrict__ normals, const double* __restrict__ uni,
+                     double sigma, double lo, double hi, float* __restrict__ actions) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float a0, a1;
+  if (i < n_warm) {   // env.action_space.sample() (train-ddpg-cnn.py:109-110)
+    const double2 u = reinterpret_cast<const double2*>(uni)[i];
+    a0 = (float)(lo + (hi - lo) * u.x);
+    a1 = (float)(lo + (hi - lo) * u.y);
+  } else {            // :112-118: float64 sum and clip, rounded once to float32
+    const float2 o = reinterpret_cast<const float2*>(actor_out)[i];
+    const double2 z = reinterpret_cast<const double2*>(normals)[i];
+    double v0 = (double)o.x + sigma * z.x, v1 = (double)o.y + sigma * z.y;
+    v0 = v0 < lo ? lo : (v0 > hi ? hi : v0);   // a NaN stays one, as torch.clamp's
+    v1 = v1 < lo ? lo : (v1 > hi ? hi : v1);
+    a0 = (float)v0;
+    a1 = (float)v1;
+  }
+  reinterpret_cast<float2*>(actions)[i] = make_float2(a0, a1);
+}
+
+__global__ void __launch_bounds__(256)
+substep_account_kernel(int n, int first, const double* __restrict__ reward,
+                       const uint8_t* __restrict__ done, uint8_t* __restrict__ alive,
+                       double* __restrict__ repeat_reward, uint8_t* __restrict__ died) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const bool al = first || alive[i] != 0;
+  double rr = first ? 0.0 : repeat_reward[i];
+  bool d = false;
+  if (al) {   // an unstepped env's reward / done entries are stale (dt_step_masked)
+    rr = rr + reward[i];
+    d = done[i] != 0;
+  }
+  repeat_reward[i] = rr;
+  died[i] = d ? 1 : 0;
+  alive[i] = (al && !d) ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(256)
+decision_account_kernel(int n, int env_timesteps, const uint8_t* __restrict__ alive,
+                        int32_t* __restrict__ episode_timesteps, uint8_t* __restrict__ done,
+                        float* __restrict__ done_float, uint8_t* __restrict__ capped) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const bool al = alive[i] != 0;
+  const int32_t t = episode_timesteps[i] + 1;             // train-ddpg-cnn.py:131
+  const bool dn = !al || t >= env_timesteps;              // :135-136
+  done[i] = dn ? 1 : 0;
+  done_float[i] = (t + 1 == env_timesteps) ? 0.0f : (dn ? 1.0f : 0.0f);   // :139
+  capped[i] = (al && dn) ? 1 : 0;
+  episode_timesteps[i] = dn ? 0 : t;                      // :105, at the reset
+}
+
+constexpr int kTakeQuads = dr::NPIX / 4;   // 4-pixel items a frame (4800)
+constexpr int kTakeBlocks = 5;             // workgroups a frame: <= 4 items a lane
+
+// blockIdx.x = (env * 3 + j) * kTakeBlocks + part.  An item is 4 pixels: a
+// float4 of a grey ring, or one 32-bit word of a palette-index ring decoded
+// by dr::kPalGray; either way a wave's loads and its 16-B stores are
+// contiguous.  (A 16-B index load would leave each lane four float4 stores 64 B
+// apart: a quarter of the bytes a store instruction could cover.)
+template <bool kIdx>
+__global__ void __launch_bounds__(256)
+stack_take_kernel(const void* __restrict__ ring, int slots, int o0, int o1, int o2,
+                  const uint8_t* __restrict__ mask, float* __restrict__ out) {
+  const int part = blockIdx.x % kTakeBlocks;
+  const int ej = blockIdx.x / kTakeBlocks;
+  const int e = ej / 3, j = ej - 3 * e;
+  if (mask && !mask[e]) return;   // workgroup-uniform
+  const int slot = j == 0 ? o0 : (j == 1 ? o1 : o2);
+  const size_t src = ((size_t)e * slots + slot) * kTakeQuads;
+  float4* __restrict__ dst = reinterpret_cast<float4*>(out) + ((size_t)e * 3 + j) * kTakeQuads;
+  for (int q = part * 256 + threadIdx.x; q < kTakeQuads; q += kTakeBlocks * 256) {
+    float4 g;
+    if (kIdx) {
+      const uint32_t v = static_cast<const uint32_t*>(ring)[src + q];
+      g.x = dr::kPalGray[v & 7u];
+      g.y = dr::kPalGray[(v >> 8) & 7u];
+      g.z = dr::kPalGray[(v >> 16) & 7u];
+      g.w = dr::kPalGray[(v >> 24) & 7u];
+    } else {
+      g = static_cast<const float4*>(ring)[src + q];
+    }
+    dst[q] = g;
+  }
+}
+
+}  // namespace
+
+extern "C" int dt_explore_gauss(int32_t n, int32_t n_warm, const float* actor_out,
+                                const double* normals, const double* uni, double sigma,
+                                double lo, double hi, float* actions, void* stream) {
+  if (n < 0 || n_warm < 0 || n_warm > n) return DT_E_ARG;
+  if (n == 0) return DT_OK;
+  if (!actions || (n_warm > 0 && !uni) || (n_warm < n && (!actor_out || !normals)))
+    return DT_E_ARG;
+  explore_gauss_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(
+      n, n_warm, actor_out, normals, uni, sigma, lo, hi, actions);
+  return hipGetLastError() == hipSuccess ? DT_OK : DT_E_HIP;
+}
+
+extern "C" int dt_substep_account(int32_t n, int32_t first, const double* reward,
+                                  const uint8_t* done, uint8_t* alive, double* repeat_reward,
+                                  uint8_t* died, void* stream) {
+  if (n < 0) return DT_E_ARG;
+  if (n == 0) return DT_OK;
+  if (!reward || !done || !alive || !repeat_reward || !died) return DT_E_ARG;
+  substep_account_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(
+      n, first != 0, reward, done, alive, repeat_reward, died);
+  return hipGetLastError() == hipSuccess ? DT_OK : DT_E_HIP;
+}
+
+extern "C" int dt_decision_account(int32_t n, int32_t env_timesteps, const uint8_t* alive,
+                                   int32_t* episode_timesteps, uint8_t* done, float* done_float,
+                                   uint8_t* capped, void* stream) {
+  if (n < 0) return DT_E_ARG;
+  if (n == 0) return DT_OK;
+  if (!alive || !episode_timesteps || !done || !done_float || !capped) return DT_E_ARG;
+  decision_account_kernel<<<(n + 255) / 256, 256, 0, (hipStream_t)stream>>>(
+      n, env_timesteps, alive, episode_timesteps, done, done_float, capped);
+  return hipGetLastError() == hipSuccess ? DT_OK : DT_E_HIP;
+}
+
+extern "C" int dt_stack_take(const void* ring, int32_t index, int32_t n, int32_t slots,
+                             const int32_t* order, const uint8_t* mask, float* out,
+                             void* stream) {
+  // n * 3 * kTakeBlocks workgroups in a 32-bit grid
+  if (n < 0 || n > (1 << 26) || slots < 1 || !order) return DT_E_ARG;
+  for (int i = 0; i < 3; ++i)
+    if (order[i] < 0 || order[i] >= slots) return DT_E_ARG;
+  if (n == 0) return DT_OK;
+  if (!ring || !out || ((reinterpret_cast<uintptr_t>(ring) | reinterpret_cast<uintptr_t>(out)) & 15))
+    return DT_E_ARG;
+  const dim3 grid((unsigned)n * 3u * kTakeBlocks);
+  if (index)
+    stack_take_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(ring, slots, order[0], order[1],
+                                                                  order[2], mask, out);
+  else
+    stack_take_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(ring, slots, order[0],
+                                                                   order[1], order[2], mask, out);
+  return hipGetLastError() == hipSuccess ? DT_OK : DT_E_HIP;
+}
+
 // ---- dt_episode_account: the explorers' episode sums and finished-episode ring -------------
 // One lane per env walks its k decisions in order (the f64 sums are the
 // explorer's `episode_metrics[...] += ...` in the same order); a finished
@@ -402,8 +556,9 @@ actor_head_kernel(int n, int n0, int k, const __half* __restrict__ h, int ld,
                   __half2float(__float2half(acc1 + __half2float(b2[1])))};
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-      if (head == 1) y[j] = tanhf(y[j]);
-      else if (head == 2) y[j] = 1.0f / (1.0f + expf(-y[j]));
+      const int hj = head == 3 ? 2 - j : head;   // 3: sigmoid on output 0, tanh on 1
+      if (hj == 1) y[j] = tanhf(y[j]);
+      else if (hj == 2) y[j] = 1.0f / (1.0f + expf(-y[j]));
     }
     *reinterpret_cast<float2*>(out + 2 * (size_t)row) = make_float2(y[0], y[1]);
   }
@@ -414,7 +569,7 @@ extern "C" int dt_actor_head(int32_t n, int32_t n0, int32_t k, const void* h, in
                              const void* w2a, const void* b2a, const void* w2b, const void* b2b,
                              int32_t head, float slope, float* out, void* stream) {
   if (n < 0 || n0 < 0 || n0 > n || k < 8 || (k & 7) != 0 || ld < k || (ld & 7) != 0 || !h ||
-      !w2a || !b2a || !out || head < 0 || head > 2 || (n0 < n && (!w2b || !b2b)))
+      !w2a || !b2a || !out || head < 0 || head > 3 || (n0 < n && (!w2b || !b2b)))
     return DT_E_ARG;
   if (((reinterpret_cast<uintptr_t>(h) | reinterpret_cast<uintptr_t>(w2a) |
         (w2b ? reinterpret_cast<uintptr_t>(w2b) : 0)) & 15) ||

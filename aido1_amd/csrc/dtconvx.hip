@@ -711,7 +711,10 @@ constexpr int kHWaves = 8, kHParts = 4, kHPartSteps = kHSteps / kHParts;   // 63
 constexpr int kHRows = 64;                                                 // samples a workgroup
 static_assert(kHSteps % kHParts == 0, "K split");
 
-__device__ __forceinline__ float head_act(float v, int head) {
+// head 3 (duckietown_rl/ddpg.py:58-60 at max_action 1): sigmoid on output 0,
+// tanh on output 1
+__device__ __forceinline__ float head_act(float v, int head, int j) {
+  if (head == 3) head = j == 0 ? 2 : 1;
   if (head == 1) return tanhf(v);
   if (head == 2) return 1.0f / (1.0f + expf(-v));
   return v;
@@ -984,7 +987,7 @@ head_finish_kernel(int n, int n0, int ldp, const float* __restrict__ part,
       float a = (float)b2[j];
 #pragma unroll
       for (int q = 0; q < 16; ++q) a += red[r2][q][j];
-      out[(size_t)orow * 2 + j] = head_act(a, head);
+      out[(size_t)orow * 2 + j] = head_act(a, head, j);
     }
   }
 }
@@ -1031,7 +1034,7 @@ int head_launch(int32_t n, int32_t n0, int32_t k, const void* x, float p, uint32
                 const T* b1b, const T* w2b, const T* b2b, int32_t head, float slope, float* work,
                 float* out, void* stream) {
   if (!x || !w1a || !b1a || !w2a || !b2a || !work || !out || n < 0 || n0 < 0 || n0 > n ||
-      k != kHK || head < 0 || head > 2 || !(p >= 0.0f && p < 1.0f))
+      k != kHK || head < 0 || head > 3 || !(p >= 0.0f && p < 1.0f))
     return DT_E_ARG;
   if (n0 < n && (!w1b || !b1b || !w2b || !b2b)) return DT_E_ARG;
   if (n == 0) return DT_OK;

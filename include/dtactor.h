@@ -174,7 +174,9 @@ int dt_conv32x_split(int32_t layer, int32_t n, const void* x, const float* wfrag
  *          (hi, lo) MFMA A fragments, element [q][t][s][l][j] = half q of
  *          w1[32 t + l % 32][16 s + 8 (l / 32) + j] (aido1_amd/actor.py)
  *   b1*    device f32 [512]; w2* device f32 [2, 512]; b2* device f32 [2]
- *   head   0 none, 1 tanh, 2 sigmoid; out device f32 [n, 2]
+ *   head   0 none, 1 tanh, 2 sigmoid, 3 sigmoid on output 0 and tanh on output
+ *          1 (duckietown_rl/ddpg.py:58-60 with max_action 1); out device f32
+ *          [n, 2]
  *   work   device f32 [dt_actor_head_x3_work_floats(n)]: lin1's partial sums
  *          (four K quarters) between the two launches it makes */
 int dt_actor_head_x3(int32_t n, int32_t n0, int32_t k, const float* x, const void* w1a,
@@ -238,6 +240,55 @@ int dt_explore(int32_t n, const float* actor_out, const double* normals, const d
  * gets its OU state zeroed and episode[i] += 1 (explorers.py:170). */
 int dt_explore_done(int32_t n, const uint8_t* done, double* ou_x, int64_t* episode,
                     float* actions, int32_t tanh_map, void* stream);
+
+/* The batched decision of duckietown_rl's own DDPG (train-ddpg-cnn.py:108-140,
+ * duckietown_rl/utils.py:60-77; aido1_amd/cnn_rollout.py), additions of ABI 14.
+ * Each of the first three is one lane an env and equals cnn_rollout.SubstepBook
+ * (torch, any device) bit for bit.
+ *
+ * dt_explore_gauss: the script's action choice.  Envs [0, n_warm) are in its
+ * uniform warm-up (:109-110): a = (float)(lo + (hi - lo) * u); the others take
+ * a = (float)clip((double)actor_out + sigma * normal, lo, hi) (:112-118: the
+ * float64 sum and clip of numpy, np.random.normal(0, sigma) = sigma * z).
+ * The one deviation from the script: it hands that float64 action to its
+ * wrappers, the step kernels take float32, so a is rounded once to float32
+ * here, before the step.
+ *   actor_out f32 [n, 2], normals f64 [n, 2] (NULL allowed when n_warm == n);
+ *   uni f64 [n, 2] in [0, 1) (NULL allowed when n_warm == 0); actions f32
+ *   [n, 2] out. */
+int dt_explore_gauss(int32_t n, int32_t n_warm, const float* actor_out, const double* normals,
+                     const double* uni, double sigma, double lo, double hi, float* actions,
+                     void* stream);
+
+/* dt_substep_account: after each of a decision's Simulator steps
+ * (train-ddpg-cnn.py:122-127).  first != 0 sets alive = 1 and repeat_reward = 0
+ * beforehand.  Where alive: repeat_reward += reward, died = done, alive &=
+ * !done; elsewhere died = 0.  It gates on alive because dt_step_masked leaves
+ * the reward / done entries of the envs it did not step as they were.
+ *   reward f64 [n], done u8 [n]: the step's outputs; alive u8 [n],
+ *   repeat_reward f64 [n] in place; died u8 [n] out. */
+int dt_substep_account(int32_t n, int32_t first, const double* reward, const uint8_t* done,
+                       uint8_t* alive, double* repeat_reward, uint8_t* died, void* stream);
+
+/* dt_decision_account: after the decision's last step (train-ddpg-cnn.py:
+ * 131-139): episode_timesteps += 1; done = !alive || episode_timesteps >=
+ * env_timesteps; done_float = (episode_timesteps + 1 == env_timesteps) ? 0 :
+ * done; capped = alive && done (the envs the cap alone ended: still to be
+ * reset); episode_timesteps = 0 where done.
+ *   alive u8 [n]; episode_timesteps i32 [n] in place; done u8 [n], done_float
+ *   f32 [n], capped u8 [n] out. */
+int dt_decision_account(int32_t n, int32_t env_timesteps, const uint8_t* alive,
+                        int32_t* episode_timesteps, uint8_t* done, float* done_float,
+                        uint8_t* capped, void* stream);
+
+/* dt_stack_take: out[e, j] = grey(ring[e, order[j]]) as float32 for the envs
+ * with mask[e] != 0 (mask NULL: every env); the other rows of out are not
+ * written.  ring: [n, slots, 120, 160], grey f32 (index == 0) or palette-index
+ * u8 (index != 0, decoded by dt_palette_gray's table bit for bit); order: 3
+ * host ints (ImgStacker's stack is newest first, duckietown_rl/wrappers.py:
+ * 65-72); out f32 [n, 3, 120, 160].  ring and out 16-byte aligned. */
+int dt_stack_take(const void* ring, int32_t index, int32_t n, int32_t slots, const int32_t* order,
+                  const uint8_t* mask, float* out, void* stream);
 
 /* dt_episode_account: the explorers' per-episode accounting for n envs, after
  * each decision (training/explorers.py:118-123 start an episode at zero,
@@ -307,7 +358,8 @@ int dt_refresh_copy(int32_t n, const DtCopyEntry* table, int64_t max_count, void
  *   h      device fp16 [n, ld] (the first linear's output, bias included), k
  *          inputs used (k, ld multiples of 8)
  *   w2*    device fp16 [2, k]; b2* device fp16 [2]
- *   head   0 none, 1 tanh, 2 sigmoid; slope the LeakyReLU's negative slope
+ *   head   0 none, 1 tanh, 2 sigmoid, 3 sigmoid | tanh (as dt_actor_head_x3's);
+ *          slope the LeakyReLU's negative slope
  *   out    device f32 [n, 2]
  * LeakyReLU is rounded to fp16 and the pre-head value to fp16, as the fp16
  * tensors of the torch path are; the dot products accumulate in f32. */
