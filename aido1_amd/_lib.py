@@ -228,6 +228,13 @@ def bind(L):
                                            vp, vp, vp, vp, vp, vp]),
         'dt_frame_gather_w': (ctypes.c_int, [i32, vp, vp, i32, i64, i32, vp, vp, vp, vp, vp,
                                              vp, vp, vp, vp, vp, vp, vp, vp]),
+        'dt_replay_claim': (ctypes.c_int, [i32, i64, i64, u64, vp, vp, vp]),
+        'dt_stack_store': (ctypes.c_int, [vp, i32, i32, ctypes.POINTER(i32), vp, vp, i32, vp,
+                                          vp]),
+        'dt_replay_commit': (ctypes.c_int, [i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        'dt_replay_draw': (ctypes.c_int, [i32, i64, i64, u64, vp, vp]),
+        'dt_cnn_replay_gather': (ctypes.c_int, [i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp,
+                                                vp, vp]),
         # dttrain.h
         'dt_train_work_floats': (i64, [i64]),
         'dt_bn_leaky_fwd': (ctypes.c_int, [i64, vp, vp, ctypes.c_float, vp, vp, ctypes.c_float,

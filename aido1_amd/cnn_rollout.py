@@ -21,6 +21,8 @@ dt_explore_gauss, dt_substep_account and dt_decision_account
 themselves, written against a small "world" (step, render, take, reset) so
 that tests drive them over the reference's own scripted run
 (tests/golden/ddpg_cnn_loop.json); ``CnnRollout`` is the world of a VecEnv.
+``collect`` stores a decision in a ddpg.ReplayBuffer (float32 stacks, host
+eviction draws) or in a cnn_replay.CnnReplay (the ring's bytes, on the device).
 
 Random numbers: one torch generator on the rollout's device.  A ``step()``
 draws, in this order and only when used, ``rand(n, 2)`` float64 for the envs
@@ -282,6 +284,14 @@ class CnnRollout:
         [n, 3, 120, 160] float32 newest first, action float32 [n, 2],
         repeat_reward float64 (the sub-steps' raw rewards added in order),
         done_float float32."""
+        self._choose(actions)
+        decide(self.book, self._world, self.action, self.state, self.next_state)
+        self.collected += self.n
+        return self.state, self.next_state, self.action, self.book.repeat_reward, \
+            self.book.done_float
+
+    def _choose(self, actions):
+        """The decision's actions into self.action (step()'s first half)."""
         n, book = self.n, self.book
         if actions is None:
             n_warm = min(n, max(0, self.start_timesteps - self.collected))
@@ -297,16 +307,31 @@ class CnnRollout:
                 book.gauss_actions(out, normals, uni, n_warm, out=self.action)
         else:
             self.action.copy_(actions)
-        decide(book, self._world, self.action, self.state, self.next_state)
-        self.collected += n
-        return self.state, self.next_state, self.action, book.repeat_reward, book.done_float
 
-    def collect(self, replay_buffer):
-        """step(), then the n transitions into a ddpg.ReplayBuffer in env
-        order (add_batch: the reference's eviction draws, on the host)."""
-        tr = self.step()
-        replay_buffer.add_batch(*tr)
-        return tr
+    def collect(self, replay_buffer, actions=None):
+        """One decision (actions as step()'s) into a replay buffer.
+
+        A ddpg.ReplayBuffer: step(), then the n transitions in env order
+        (add_batch: the reference's eviction draws, on the host); returns
+        step()'s tensors.  A cnn_replay.CnnReplay: the slots are claimed
+        first and the decision's own takes write the ring's bytes into them
+        (dt_stack_store), so no float32 stack is produced; then the scalars;
+        returns the claimed rows (int64 [n], -1 where a later transition of
+        the batch evicted this one)."""
+        from aido1_amd.cnn_replay import CnnReplay
+        if not isinstance(replay_buffer, CnnReplay):
+            tr = self.step(actions)
+            replay_buffer.add_batch(*tr)
+            return tr
+        if self.frames != 'index':
+            raise ValueError("CnnReplay stores the ring's palette-index bytes: a rollout built "
+                             "with frames=%r collects into a ddpg.ReplayBuffer" % (self.frames,))
+        self._choose(actions)
+        rows = replay_buffer.claim(self.n)
+        decide(self.book, _StoreWorld(self._world, replay_buffer), self.action, 0, 1)
+        replay_buffer.commit(self.action, self.book.repeat_reward, self.book.done_float)
+        self.collected += self.n
+        return rows
 
     def evaluate_policy(self, max_timesteps=1000, eval_episodes=10, env_id_base=None):
         """duckietown_rl/utils.py:60-77, batched: eval_episodes envs of their
@@ -384,3 +409,18 @@ class _EnvWorld:
         with self.owner._phase('reset'):
             env._check(env._L.dt_reset(env._h, mask.data_ptr() if mask is not None else None,
                                        env._stream()), 'dt_reset')
+
+
+class _StoreWorld:
+    """An _EnvWorld whose take(mask, half) writes the ring's bytes into a
+    CnnReplay's claimed rows (half 0: state, 1: next_state) instead of
+    decoding them into a float32 stack; step, render and reset are the
+    world's own."""
+
+    def __init__(self, world, replay):
+        self.world, self.replay = world, replay
+        self.step, self.render, self.reset = world.step, world.render, world.reset
+
+    def take(self, mask, half):
+        with self.world.owner._phase('take'):
+            self.replay.store(self.world.out.ring, self.world.order(), mask, half)

@@ -17,6 +17,7 @@
 
 #include "../../include/dtreplay.h"
 #include "dtrender.h"   // dr::kPalGray (palette-index frames)
+#include "dtsim_common.h"   // dt::philox (CnnReplay's eviction and sampling draws)
 
 struct dt_per {
   int device = 0;
@@ -468,7 +469,131 @@ frame_add_kernel(int64_t frame4, const float4* __restrict__ src, int64_t src_str
   }
 }
 
-#define PER_HIP(h, expr)                                                       \
+// ---- CnnReplay's kernels (include/dtreplay.h, the last five entry points) ----------------
+constexpr int kClaimThreads = 256;
+constexpr uint32_t kTagEvict = 0x45564943u;    // 'EVIC': the slot a full buffer's add evicts
+constexpr uint32_t kTagSample = 0x534D504Cu;   // 'SMPL': the slot a draw reads
+constexpr int kStoreFrame16 = dr::NPIX / 16;   // 16-B items of a byte frame (1200)
+constexpr int kStoreQuads = dr::NPIX / 4;      // 4-pixel words of a byte frame (4800)
+// (word 0 of the serial's block * range) >> 32: uniform over [0, range)
+__device__ __forceinline__ uint64_t replay_pick(uint64_t serial, uint32_t tag, uint64_t range,
+                                                uint32_t k0, uint32_t k1) {
+  const dt::U4 w = dt::philox((uint32_t)serial, (uint32_t)(serial >> 32), 0u, tag, k0, k1);
+  return ((uint64_t)w.a * range) >> 32;
+}
+
+// phase 0: every add bids its serial + 1 for its slot; phase 1 (a second
+// launch, so every bid has landed): the add that holds the slot keeps it
+__global__ void __launch_bounds__(kClaimThreads)
+replay_claim_kernel(int n, uint64_t added, uint64_t max_size, uint32_t k0, uint32_t k1,
+                    unsigned long long* __restrict__ owner, int64_t* __restrict__ rows, int phase) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t s = added + (uint64_t)i;
+  const uint64_t slot = s < max_size ? s : replay_pick(s, kTagEvict, max_size, k0, k1);
+  if (phase == 0)
+    atomicMax(&owner[slot], (unsigned long long)(s + 1));
+  else
+    rows[i] = owner[slot] == s + 1 ? (int64_t)slot : (int64_t)-1;
+}
+
+// blockIdx.x = env * 3 + j: one workgroup copies one 19,200-B frame, 16 B a
+// lane an item, a wave's loads and stores contiguous; every load is issued
+// before the first store
+__global__ void __launch_bounds__(kFrameThreads)
+stack_store_kernel(const uint4* __restrict__ ring, int slots, int o0, int o1, int o2,
+                   const uint8_t* __restrict__ mask, const int64_t* __restrict__ rows, int half,
+                   uint4* __restrict__ frames) {
+  const int e = blockIdx.x / 3, j = blockIdx.x - 3 * e;
+  if (mask && !mask[e]) return;   // workgroup-uniform
+  const int64_t row = rows[e];
+  if (row < 0) return;            // workgroup-uniform: a later add of the batch took the slot
+  const int slot = j == 0 ? o0 : (j == 1 ? o1 : o2);
+  const uint4* __restrict__ src = ring + ((size_t)e * slots + slot) * kStoreFrame16;
+  uint4* __restrict__ dst = frames + ((size_t)row * 6 + 3 * half + j) * kStoreFrame16;
+  static_assert(kStoreFrame16 > 4 * kFrameThreads && kStoreFrame16 <= 5 * kFrameThreads,
+                "four full rounds and a tail");
+  const int t = threadIdx.x;
+  const bool tail = t + 4 * kFrameThreads < kStoreFrame16;
+  const uint4 a0 = src[t], a1 = src[t + kFrameThreads], a2 = src[t + 2 * kFrameThreads],
+              a3 = src[t + 3 * kFrameThreads];
+  uint4 a4 = make_uint4(0u, 0u, 0u, 0u);
+  if (tail) a4 = src[t + 4 * kFrameThreads];
+  dst[t] = a0;
+  dst[t + kFrameThreads] = a1;
+  dst[t + 2 * kFrameThreads] = a2;
+  dst[t + 3 * kFrameThreads] = a3;
+  if (tail) dst[t + 4 * kFrameThreads] = a4;
+}
+
+__global__ void __launch_bounds__(kClaimThreads)
+replay_commit_kernel(int n, const int64_t* __restrict__ rows, const float* __restrict__ action,
+                     const double* __restrict__ repeat_reward,
+                     const float* __restrict__ done_float, float* __restrict__ act_store,
+                     float* __restrict__ rew_store, float* __restrict__ done_store) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t row = rows[i];
+  if (row < 0) return;
+  reinterpret_cast<float2*>(act_store)[row] = reinterpret_cast<const float2*>(action)[i];
+  rew_store[row] = (float)repeat_reward[i];
+  done_store[row] = done_float[i];
+}
+
+__global__ void __launch_bounds__(kClaimThreads)
+replay_draw_kernel(int batch, uint64_t drawn, uint64_t len, uint32_t k0, uint32_t k1,
+                   int64_t* __restrict__ idx) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= batch) return;
+  idx[i] = (int64_t)replay_pick(drawn + (uint64_t)i, kTagSample, len, k0, k1);
+}
+
+// blockIdx.y = 2 * b + half, blockIdx.x * threads + lane = a 4-pixel item of
+// the stack: one 32-bit load a frame, decoded by dr::kPalGray exactly as
+// stack_take_kernel (dtactor.hip) decodes it.  Channels-last: the item's
+// twelve floats (4 pixels x 3 channels) are consecutive, three float4 stores
+// a lane and a wave's stores one contiguous 3 KB run.  Planes: one float4 a
+// frame, each store instruction contiguous across the wave.
+template <bool kNhwc>
+__global__ void __launch_bounds__(kFrameThreads)
+cnn_replay_gather_kernel(const int64_t* __restrict__ idx, const uint32_t* __restrict__ frames,
+                         const float* __restrict__ act_store, const float* __restrict__ rew_store,
+                         const float* __restrict__ done_store, float* __restrict__ obs,
+                         float* __restrict__ nxt, float* __restrict__ act, float* __restrict__ rew,
+                         float* __restrict__ done) {
+  const int b = blockIdx.y >> 1, half = blockIdx.y & 1;
+  const int64_t i = idx[b];
+  if (blockIdx.x == 0 && half == 0) {
+    if (threadIdx.x < 2) act[2 * b + threadIdx.x] = act_store[2 * i + threadIdx.x];
+    if (threadIdx.x == 2) rew[b] = rew_store[i];
+    if (threadIdx.x == 3) done[b] = done_store[i];
+  }
+  const int q = blockIdx.x * kFrameThreads + threadIdx.x;
+  if (q >= kStoreQuads) return;
+  const uint32_t* __restrict__ src = frames + ((size_t)i * 6 + 3 * half) * kStoreQuads + q;
+  float4* __restrict__ dst = reinterpret_cast<float4*>(half ? nxt : obs) + (size_t)b * 3 * kStoreQuads;
+  uint32_t v[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) v[c] = src[(size_t)c * kStoreQuads];
+  if (kNhwc) {
+    float g[12];
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) g[3 * p + c] = dr::kPalGray[(v[c] >> (8 * p)) & 7u];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      dst[(size_t)3 * q + k] = make_float4(g[4 * k], g[4 * k + 1], g[4 * k + 2], g[4 * k + 3]);
+  } else {
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      dst[(size_t)c * kStoreQuads + q] =
+          make_float4(dr::kPalGray[v[c] & 7u], dr::kPalGray[(v[c] >> 8) & 7u],
+                      dr::kPalGray[(v[c] >> 16) & 7u], dr::kPalGray[(v[c] >> 24) & 7u]);
+  }
+}
+
+#define PER_HIP(h, expr)                                                      \
   do {                                                                         \
     hipError_t _e = (expr);                                                    \
     if (_e != hipSuccess) {                                                    \
@@ -652,6 +777,92 @@ int dt_frame_gather_w(int32_t batch, const int64_t* idx, const void* frames, int
     frame_gather_kernel<<<grid, kFrameThreads, 0, (hipStream_t)stream>>>(
         idx, static_cast<const float*>(frames), hw, k, obs_ptr, next_ptr, action, reward, done,
         obs, nxt, act, rew, notdone, weights, w);
+  return hipGetLastError() == hipSuccess ? DT_OK : DT_E_HIP;
+}
+
+// ---- device replay of the batched train-ddpg-cnn.py rollout (aido1_amd/cnn_replay.py) -----
+// Slot-form ReplayBuffer (duckietown_rl/utils.py:18-57): the slot of an add
+// and of a draw is a pure function of its serial (Philox4x32-10, the spawn
+// path's generator), so no state but `owner` lives on the device and every
+// integer here is the one cnn_replay.py's torch path computes.
+int dt_replay_claim(int32_t n, int64_t added, int64_t max_size, uint64_t seed, uint64_t* owner,
+                    int64_t* rows, void* stream) {
+  if (n < 0 || added < 0 || max_size < 1 || max_size >= (int64_t(1) << 31)) return DT_E_ARG;
+  if (n == 0) return DT_OK;
+  if (!owner || !rows) return DT_E_ARG;
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  const int grid = (n + kClaimThreads - 1) / kClaimThreads;
+  // two launches: every atomicMax of the batch lands before any lane reads
+  for (int phase = 0; phase < 2; ++phase)
+    replay_claim_kernel<<<grid, kClaimThreads, 0, (hipStream_t)stream>>>(
+        n, (uint64_t)added, (uint64_t)max_size, k0, k1,
+        reinterpret_cast<unsigned long long*>(owner), rows, phase);
+  return hipGetLastError() == hipSuccess ? DT_OK : DT_E_HIP;
+}
+
+int dt_stack_store(const uint8_t* ring, int32_t n, int32_t slots, const int32_t* order,
+                   const uint8_t* mask, const int64_t* rows, int32_t half, uint8_t* frames,
+                   void* stream) {
+  // n * 3 workgroups in a 32-bit grid
+  if (n < 0 || n > (1 << 26) || slots < 1 || !order || half < 0 || half > 1) return DT_E_ARG;
+  for (int i = 0; i < 3; ++i)
+    if (order[i] < 0 || order[i] >= slots) return DT_E_ARG;
+  if (n == 0) return DT_OK;
+  if (!ring || !rows || !frames) return DT_E_ARG;
+  if ((reinterpret_cast<uintptr_t>(ring) | reinterpret_cast<uintptr_t>(frames)) & 15)
+    return DT_E_ARG;
+  stack_store_kernel<<<(unsigned)n * 3u, kFrameThreads, 0, (hipStream_t)stream>>>(
+      reinterpret_cast<const uint4*>(ring), slots, order[0], order[1], order[2], mask, rows, half,
+      reinterpret_cast<uint4*>(frames));
+  return hipGetLastError() == hipSuccess ? DT_OK : DT_E_HIP;
+}
+
+int dt_replay_commit(int32_t n, const int64_t* rows, const float* action,
+                     const double* repeat_reward, const float* done_float, float* act_store,
+                     float* rew_store, float* done_store, void* stream) {
+  if (n < 0) return DT_E_ARG;
+  if (n == 0) return DT_OK;
+  if (!rows || !action || !repeat_reward || !done_float || !act_store || !rew_store ||
+      !done_store)
+    return DT_E_ARG;
+  replay_commit_kernel<<<(n + kClaimThreads - 1) / kClaimThreads, kClaimThreads, 0,
+                         (hipStream_t)stream>>>(n, rows, action, repeat_reward, done_float,
+                                                act_store, rew_store, done_store);
+  return hipGetLastError() == hipSuccess ? DT_OK : DT_E_HIP;
+}
+
+int dt_replay_draw(int32_t batch, int64_t drawn, int64_t len, uint64_t seed, int64_t* idx,
+                   void* stream) {
+  if (batch < 0 || drawn < 0) return DT_E_ARG;
+  if (batch == 0) return DT_OK;
+  if (len < 1 || len >= (int64_t(1) << 31) || !idx) return DT_E_ARG;
+  replay_draw_kernel<<<(batch + kClaimThreads - 1) / kClaimThreads, kClaimThreads, 0,
+                       (hipStream_t)stream>>>(batch, (uint64_t)drawn, (uint64_t)len,
+                                              (uint32_t)seed, (uint32_t)(seed >> 32), idx);
+  return hipGetLastError() == hipSuccess ? DT_OK : DT_E_HIP;
+}
+
+int dt_cnn_replay_gather(int32_t batch, const int64_t* idx, const uint8_t* frames,
+                         const float* act_store, const float* rew_store, const float* done_store,
+                         int32_t nhwc, float* obs, float* nxt, float* act, float* rew,
+                         float* done, void* stream) {
+  if (batch < 0 || batch > 32767) return DT_E_ARG;   // 2 * batch rows of a 16-bit grid.y
+  if (batch == 0) return DT_OK;
+  if (!idx || !frames || !act_store || !rew_store || !done_store || !obs || !nxt || !act ||
+      !rew || !done)
+    return DT_E_ARG;
+  if ((reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(obs) |
+       reinterpret_cast<uintptr_t>(nxt)) & 15)
+    return DT_E_ARG;
+  const dim3 grid((kStoreQuads + kFrameThreads - 1) / kFrameThreads, 2u * (unsigned)batch);
+  if (nhwc)
+    cnn_replay_gather_kernel<true><<<grid, kFrameThreads, 0, (hipStream_t)stream>>>(
+        idx, reinterpret_cast<const uint32_t*>(frames), act_store, rew_store, done_store, obs, nxt,
+        act, rew, done);
+  else
+    cnn_replay_gather_kernel<false><<<grid, kFrameThreads, 0, (hipStream_t)stream>>>(
+        idx, reinterpret_cast<const uint32_t*>(frames), act_store, rew_store, done_store, obs, nxt,
+        act, rew, done);
   return hipGetLastError() == hipSuccess ? DT_OK : DT_E_HIP;
 }
 

@@ -130,6 +130,63 @@ int dt_frame_gather_w(int32_t batch, const int64_t* idx, const void* frames, int
                       float* nxt, float* act, float* rew, float* notdone, const double* weights,
                       float* w, void* stream);
 
+/* ---- device replay of the batched train-ddpg-cnn.py rollout (aido1_amd/cnn_replay.py) ----
+ * New entry points only: no existing signature or layout changes, so
+ * DT_ABI_VERSION stays 14.
+ *
+ * duckietown_rl/utils.py:18-57 (ReplayBuffer) in slot form.  Transition s (the
+ * 0-based count of every add) takes slot s while s < max_size; later it evicts
+ * slot (w * max_size) >> 32 (64-bit), w = word 0 of philox4x32_10((lo32(s),
+ * hi32(s), 0, 'EVIC' = 0x45564943), (lo32(seed), hi32(seed))).  Draw d (the
+ * count of every draw) reads slot (w * len) >> 32, w from the block tagged
+ * 'SMPL' = 0x534D504C with d in s's place.  A transition is six palette-index
+ * byte frames (state 0-2, next_state 3-5, each newest first) and 16 B of
+ * scalars.  All five calls are stateless, validate on the host (DT_E_ARG
+ * before any launch) and never synchronise. */
+
+/* n adds with serials added .. added + n - 1.  owner: device u64 [max_size],
+ * zero at creation, never cleared: each lane does atomicMax(owner[slot],
+ * s + 1), then rows[i] (device i64 [n]) = slot where owner[slot] == s + 1,
+ * else -1: of two adds of this batch to one slot the later keeps it, as
+ * sequential adds would leave it.  Afterwards owner[slot] - 1 is the serial
+ * the slot holds.  1 <= max_size < 2^31. */
+int dt_replay_claim(int32_t n, int64_t added, int64_t max_size, uint64_t seed, uint64_t* owner,
+                    int64_t* rows, void* stream);
+
+/* The byte twin of dt_stack_take (dtactor.h): for every env e < n with
+ * mask[e] != 0 (mask NULL: every env) and rows[e] >= 0,
+ *   frames[rows[e]][3 * half + j] = ring[e][order[j]]   (j < 3, 19,200 B verbatim)
+ * ring: device u8 [n, slots, 120, 160] (an index ring), frames: device u8
+ * [max_size, 6, 120, 160], both 16-B aligned; order[3] host, each in
+ * [0, slots); half 0 (state) or 1 (next_state). */
+int dt_stack_store(const uint8_t* ring, int32_t n, int32_t slots, const int32_t* order,
+                   const uint8_t* mask, const int64_t* rows, int32_t half, uint8_t* frames,
+                   void* stream);
+
+/* The scalars of the envs with rows[e] >= 0: act_store[rows[e]] = action[e]
+ * (f32 x 2), rew_store = (float)repeat_reward[e] (f64 -> f32, as
+ * ddpg.ReplayBuffer stores it), done_store = done_float[e]. */
+int dt_replay_commit(int32_t n, const int64_t* rows, const float* action,
+                     const double* repeat_reward, const float* done_float, float* act_store,
+                     float* rew_store, float* done_store, void* stream);
+
+/* Draws drawn .. drawn + batch - 1 over len = min(added, max_size) filled
+ * slots into idx (device i64 [batch]).  1 <= len < 2^31. */
+int dt_replay_draw(int32_t batch, int64_t drawn, int64_t len, uint64_t seed, int64_t* idx,
+                   void* stream);
+
+/* The sampled batch in the layout ddpg.DDPG.train reads: obs / nxt float32
+ * [batch, 3, 120, 160] = dt_palette_gray's table over frames[idx[b]][0..2] /
+ * [3..5] (bit for bit dt_stack_take's decode), as planes (nhwc == 0) or in
+ * channels-last memory (nhwc != 0: obs[b][y][x][c]); act [batch, 2], rew
+ * [batch, 1], done [batch, 1] copied.  idx device i64 [batch], unchecked
+ * (dt_replay_draw's or dt_replay_claim's output), may repeat a slot.  frames,
+ * obs and nxt 16-B aligned. */
+int dt_cnn_replay_gather(int32_t batch, const int64_t* idx, const uint8_t* frames,
+                         const float* act_store, const float* rew_store, const float* done_store,
+                         int32_t nhwc, float* obs, float* nxt, float* act, float* rew,
+                         float* done, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
