@@ -4,6 +4,8 @@
 #include <string>
 #include <vector>
 
+#include "dtdevbuf.h"
+#include "dtrecords.h"
 #include "dtrender.h"
 #include "dtsim_common.h"
 
@@ -20,18 +22,18 @@ struct dt_handle {
   dt::Geo geo{};
   StepCfg sc{};
   dt::MapDev map{};
-  void* map_buf = nullptr;
+  DevBuf map_buf;
   dt::State st{};
-  void* st_buf = nullptr;
+  DevBuf st_buf;
   size_t lds_bytes = 0;     // the map image the kernels stage (walker rows included)
   uint32_t env_base = 0;
   // observation path (dtrender.hip)
   dt_line_params line_params{};
   dr::LineDev line{};
-  void* mark_buf = nullptr;   // float4 segments (x0, z0, x1, z1): yellow then white
+  DevBuf mark_buf;   // float4 segments (x0, z0, x1, z1): yellow then white
   int32_t n_yellow = 0, n_white = 0;
-  void* render_spill = nullptr;  // per env: listed words past the LDS list (dtrender.hip)
-  void* render_sched = nullptr;  // render_kernel's dispatch order state (dtrender.hip)
+  DevBuf render_spill;           // per env: listed words past the LDS list (dtrender.hip)
+  DevBuf render_sched;           // render_kernel's dispatch order state (dtrender.hip)
   uint32_t render_launches = 0;  // dt_render launches (the order's double-buffer parity)
   // the last render launch that used the dispatch-order state: its stream; a
   // render on another stream records the event there and waits for it
@@ -39,27 +41,31 @@ struct dt_handle {
   hipStream_t render_stream = nullptr;
   bool render_pending = false;
   // dt_render_objects: the footprint records the render draws (0: none)
-  void* render_objs = nullptr;   // float [DT_MAX_RENDER_OBJECTS][DT_RENDER_OBJ_STRIDE]
+  DevBuf render_objs;   // float [DT_MAX_RENDER_OBJECTS][DT_RENDER_OBJ_STRIDE]
   int32_t n_render_objs = 0;
   // dt_render_walkers: a row per record above (0: none walk)
-  void* render_walk = nullptr;   // float [DT_MAX_RENDER_OBJECTS][DT_RENDER_WALK_STRIDE]
+  DevBuf render_walk;   // float [DT_MAX_RENDER_OBJECTS][DT_RENDER_WALK_STRIDE]
   int32_t n_render_walk = 0;
   std::vector<uint8_t> render_walker;   // [n_render_walk]: the record walks (K != 0)
   // dt_set_walkers' packed rows (empty: none) and dt_set_bots' table: the two
   // share the map's mover rows, which set_movers (dtsim.hip) composes
   std::vector<double> walk_rows_host;   // [n_obj][dt::kWalkRec]
   std::vector<int32_t> bot_row;         // [n_bots] rows of dt_map.objects
-  void* bot_tab = nullptr;              // double [bot_rows][n_bots][DT_OBJ_STRIDE]
+  DevBuf bot_tab;                       // double [bot_rows][n_bots][DT_OBJ_STRIDE]
   int32_t bot_rows = 0;
   // dt_render_bots: the frame's bot table and each bot's render record (0: none)
-  void* render_bot_tab = nullptr;       // float [rows][n][DT_RENDER_OBJ_STRIDE]
-  void* render_bot_col = nullptr;       // int32 [DT_MAX_RENDER_OBJECTS]: column or -1
+  DevBuf render_bot_tab;                // float [rows][n][DT_RENDER_OBJ_STRIDE]
+  DevBuf render_bot_col;                // int32 [DT_MAX_RENDER_OBJECTS]: column or -1
   int32_t n_render_bots = 0, render_bot_rows = 0;
   std::vector<int32_t> render_bot_row;  // [n_render_bots] records of dt_render_objects
   // dt_render_camera: the forward view's gather table (on: the kCam kernels run)
-  void* render_cam = nullptr;           // uint16 [120 * 160], allocated once
+  DevBuf render_cam;                    // uint16 [120 * 160], allocated once
   bool render_cam_on = false;
   std::string err;
+  // (the caller has made `device` current: dt_destroy, dt_create)
+  ~dt_handle() {
+    if (render_done) (void)hipEventDestroy(render_done);
+  }
 };
 
 // Launch entry points run on the handle's GPU whatever the calling thread's
@@ -84,15 +90,26 @@ struct DevGuard {
 // record a failed HIP call in the handle and return DT_E_HIP
 #define HIP_OR_FAIL(h, expr)                                                   \
   do {                                                                         \
-    hipError_t _e = (expr);                                                    \
-    if (_e != hipSuccess) {                                                    \
-      (h)->err = std::string(#expr) + ": " + hipGetErrorString(_e);             \
-      return DT_E_HIP;                                                         \
-    }                                                                          \
+    if (hip_said((h)->err, #expr, (expr)) != hipSuccess) return DT_E_HIP;      \
   } while (0)
+
+// upload_in_place (dtdevbuf.h) into the handle's `buf`, failing as HIP_OR_FAIL
+// does, with its text for the three calls written out
+#define UPLOAD_IN_PLACE_OR_FAIL(h, buf, capacity, src, bytes)                  \
+  do {                                                                         \
+    const UploadCalls _c = {                                                   \
+        "hipMalloc(&h->" #buf ", " #capacity ")", "hipDeviceSynchronize()",    \
+        "hipMemcpy(h->" #buf ", " #src ", " #bytes ", hipMemcpyHostToDevice)"}; \
+    if (upload_in_place((h)->buf, capacity, src, bytes, _c, (h)->err) != hipSuccess) \
+      return DT_E_HIP;                                                         \
+  } while (0)
+
+// a dtrecords.h check's text: into the handle with DT_E_ARG, DT_OK for none
+inline int refused(dt_handle* h, const std::string& why) {
+  if (why.empty()) return DT_OK;
+  h->err = why;
+  return DT_E_ARG;
+}
 
 // dtrender.hip: lane-marking polylines of the map + default line params
 int dt_render_init(dt_handle* h, const dt_map* map);
-void dt_render_free(dt_handle* h);
-
-

@@ -2185,11 +2185,11 @@ int dt_render_init(dt_handle* h, const dt_map* map) {
   std::vector<float4> all(yellow);
   all.insert(all.end(), white.begin(), white.end());
   if (!all.empty()) {
-    if (hipMalloc(&h->mark_buf, all.size() * sizeof(float4)) != hipSuccess) {
+    if (h->mark_buf.alloc(all.size() * sizeof(float4)) != hipSuccess) {
       h->err = "hipMalloc(markings) failed";
       return DT_E_HIP;
     }
-    if (hipMemcpy(h->mark_buf, all.data(), all.size() * sizeof(float4), hipMemcpyHostToDevice) !=
+    if (hipMemcpy(h->mark_buf.ptr, all.data(), h->mark_buf.bytes, hipMemcpyHostToDevice) !=
         hipSuccess) {
       h->err = "hipMemcpy(markings) failed";
       return DT_E_HIP;
@@ -2199,7 +2199,7 @@ int dt_render_init(dt_handle* h, const dt_map* map) {
   h->line = to_line_dev(h->line_params);
   // overflow store of the render's listed words (RenderLds: slots past the
   // LDS list; never touched on the shipped maps, sized for a whole frame)
-  if (hipMalloc(&h->render_spill, (size_t)h->n * kSpillHalves * sizeof(uint16_t)) != hipSuccess) {
+  if (h->render_spill.alloc((size_t)h->n * kSpillHalves * sizeof(uint16_t)) != hipSuccess) {
     h->err = "hipMalloc(render spill) failed";
     return DT_E_HIP;
   }
@@ -2207,37 +2207,13 @@ int dt_render_init(dt_handle* h, const dt_map* map) {
   std::vector<uint32_t> sch((size_t)kSchedHead + 3 * (size_t)h->n, 0u);
   for (int k = 0; k < 2; ++k)
     for (int i = 0; i < h->n; ++i) sch[kSchedHead + (size_t)h->n * (1 + k) + i] = (uint32_t)i;
-  if (hipMalloc(&h->render_sched, sch.size() * sizeof(uint32_t)) != hipSuccess ||
-      hipMemcpy(h->render_sched, sch.data(), sch.size() * sizeof(uint32_t),
+  if (h->render_sched.alloc(sch.size() * sizeof(uint32_t)) != hipSuccess ||
+      hipMemcpy(h->render_sched.ptr, sch.data(), sch.size() * sizeof(uint32_t),
                 hipMemcpyHostToDevice) != hipSuccess) {
     h->err = "render dispatch order state: hipMalloc / hipMemcpy failed";
     return DT_E_HIP;
   }
   return DT_OK;
-}
-
-void dt_render_free(dt_handle* h) {
-  if (h->mark_buf) (void)hipFree(h->mark_buf);
-  h->mark_buf = nullptr;
-  if (h->render_spill) (void)hipFree(h->render_spill);
-  h->render_spill = nullptr;
-  if (h->render_sched) (void)hipFree(h->render_sched);
-  h->render_sched = nullptr;
-  if (h->render_done) (void)hipEventDestroy(h->render_done);
-  h->render_done = nullptr;
-  if (h->render_objs) (void)hipFree(h->render_objs);
-  h->render_objs = nullptr;
-  h->n_render_objs = 0;
-  if (h->render_walk) (void)hipFree(h->render_walk);
-  h->render_walk = nullptr;
-  h->n_render_walk = 0;
-  if (h->render_bot_tab) (void)hipFree(h->render_bot_tab);
-  if (h->render_bot_col) (void)hipFree(h->render_bot_col);
-  h->render_bot_tab = h->render_bot_col = nullptr;
-  h->n_render_bots = 0;
-  if (h->render_cam) (void)hipFree(h->render_cam);
-  h->render_cam = nullptr;
-  h->render_cam_on = false;
 }
 
 extern "C" {
@@ -2386,7 +2362,7 @@ static int render_launch(dt_handle* h, const dt_render_io* io, const dt_render_i
   a.height = h->map.height;
   a.inv_ts = (float)(1.0 / h->cfg.road_tile_size);
   a.cam_fwd = h->cfg.camera_forward_dist;
-  a.marks = (const float4*)h->mark_buf;
+  a.marks = (const float4*)h->mark_buf.ptr;
   a.n_yellow = h->n_yellow;
   a.n_white = h->n_white;
   a.gray = io->gray;
@@ -2398,7 +2374,7 @@ static int render_launch(dt_handle* h, const dt_render_io* io, const dt_render_i
   a.rgb = io->rgb;
   a.line = h->line;
   a.n = h->n;
-  a.spill = (uint16_t*)h->render_spill;
+  a.spill = (uint16_t*)h->render_spill.ptr;
 #ifndef DTSIM_NO_SCHED   // diagnostic builds only (A/B of the dispatch order)
   // a launch of <= kSchedTail workgroups runs all at once: no drain to order.
   // The order state is one per handle, double-buffered by the host's launch
@@ -2410,7 +2386,7 @@ static int render_launch(dt_handle* h, const dt_render_io* io, const dt_render_i
   if (hipStreamIsCapturing((hipStream_t)stream, &cap) != hipSuccess)
     cap = hipStreamCaptureStatusNone;
   a.sched = h->n > kSchedTail && cap == hipStreamCaptureStatusNone
-                ? (uint32_t*)h->render_sched : nullptr;
+                ? (uint32_t*)h->render_sched.ptr : nullptr;
   if (a.sched && h->render_pending && (hipStream_t)stream != h->render_stream) {
     // the stream changed: this launch waits for what the last one's stream
     // holds now (that launch included).  The event is recorded here, not
@@ -2447,19 +2423,19 @@ static int render_launch(dt_handle* h, const dt_render_io* io, const dt_render_i
   }
   const int grid = DTSIM_RENDER_SEQ ? h->n : a.parts * h->n;
   const bool big_r = a.line.dil_r >= 2;
-  a.objs = (const float4*)h->render_objs;
+  a.objs = (const float4*)h->render_objs.ptr;
   a.n_objs = h->n_render_objs;
-  a.walk = h->n_render_walk > 0 ? (const float4*)h->render_walk : nullptr;
+  a.walk = h->n_render_walk > 0 ? (const float4*)h->render_walk.ptr : nullptr;
   // never null, whichever kernel runs: an entry not given is the handle's own
   a.step_count = times && times[0] ? times[0] : h->st.step_count;
   a.time2 = io2 && times && times[1] ? times[1] : h->st.step_count;
   a.time3 = io3 && times && times[2] ? times[2] : h->st.step_count;
   const bool bots = a.n_objs > 0 && h->n_render_bots > 0;
-  a.bots = bots ? (const float4*)h->render_bot_tab : nullptr;
-  a.bot_col = (const int32_t*)h->render_bot_col;
+  a.bots = bots ? (const float4*)h->render_bot_tab.ptr : nullptr;
+  a.bot_col = (const int32_t*)h->render_bot_col.ptr;
   a.bot_rows = (uint32_t)h->render_bot_rows;
   a.n_bots = (uint32_t)h->n_render_bots;
-  a.cam = h->render_cam_on ? (const uint2*)h->render_cam : nullptr;
+  a.cam = h->render_cam_on ? (const uint2*)h->render_cam.ptr : nullptr;
   const RenderKernel kern = a.cam ? pick_render<true>(a.index != nullptr, big_r, bots, a.n_objs > 0)
                                   : pick_render<false>(a.index != nullptr, big_r, bots, a.n_objs > 0);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(kRenderThreads), 0, (hipStream_t)stream, a);
@@ -2477,31 +2453,10 @@ static int render_launch(dt_handle* h, const dt_render_io* io, const dt_render_i
 
 int dt_render_objects(dt_handle* h, const float* recs, int32_t n) {
   if (!h) return DT_E_ARG;
-  if (n < 0 || n > DT_MAX_RENDER_OBJECTS) {
-    h->err = "dt_render_objects: n must be in 0..256";
-    return DT_E_ARG;
-  }
-  if (n > 0 && !recs) {
-    h->err = "dt_render_objects: recs is null";
-    return DT_E_ARG;
-  }
-  for (int i = 0; i < n * DT_RENDER_OBJ_STRIDE; ++i)
-    if (!isfinite(recs[i])) {
-      h->err = "dt_render_objects: record " + std::to_string(i / DT_RENDER_OBJ_STRIDE) +
-               " holds a non-finite value";
-      return DT_E_ARG;
-    }
+  if (const int rc = refused(h, dtrec::objects("dt_render_objects", recs, n))) return rc;
   DevGuard dg(h->device);
-  // launches in flight read the records: wait for them (synchronous, as dt_seed)
-  HIP_OR_FAIL(h, hipDeviceSynchronize());
-  if (n > 0) {
-    // one buffer for the handle's life, of the largest size: a launch captured
-    // into a graph keeps a valid pointer whatever is uploaded later
-    const size_t rec = DT_RENDER_OBJ_STRIDE * sizeof(float);
-    if (!h->render_objs)
-      HIP_OR_FAIL(h, hipMalloc(&h->render_objs, DT_MAX_RENDER_OBJECTS * rec));
-    HIP_OR_FAIL(h, hipMemcpy(h->render_objs, recs, (size_t)n * rec, hipMemcpyHostToDevice));
-  }
+  const size_t rec = DT_RENDER_OBJ_STRIDE * sizeof(float);
+  UPLOAD_IN_PLACE_OR_FAIL(h, render_objs, DT_MAX_RENDER_OBJECTS * rec, recs, (size_t)n * rec);
   if (n != h->n_render_objs) {   // the rows matched the old records
     h->n_render_walk = 0;
     h->render_walker.clear();
@@ -2513,52 +2468,14 @@ int dt_render_objects(dt_handle* h, const float* recs, int32_t n) {
 
 int dt_render_walkers(dt_handle* h, const float* recs, int32_t n) {
   if (!h) return DT_E_ARG;
-  if (n != 0 && n != h->n_render_objs) {
-    h->err = "dt_render_walkers: n must be 0 or the count dt_render_objects was given (" +
-             std::to_string(h->n_render_objs) + ")";
-    return DT_E_ARG;
-  }
-  if (n > 0 && !recs) {
-    h->err = "dt_render_walkers: recs is null";
-    return DT_E_ARG;
-  }
-  for (int o = 0; o < n; ++o) {
-    const float* r = recs + (size_t)o * DT_RENDER_WALK_STRIDE;
-    const std::string row = "dt_render_walkers: row " + std::to_string(o);
-    bool zero = true;
-    for (int i = 0; i < DT_RENDER_WALK_STRIDE; ++i) {
-      if (!isfinite(r[i])) {
-        h->err = row + " holds a non-finite value";
-        return DT_E_ARG;
-      }
-      zero = zero && r[i] == 0.0f;
-    }
-    if (zero) continue;   // a static object
-    const bool steps = r[2] >= 0.0f && r[2] < 16777216.0f && r[2] == floorf(r[2]) &&
-                       r[3] >= 0.0f && r[3] < 16777216.0f && r[3] == floorf(r[3]);
-    if (!steps) {
-      h->err = row + ": W and K must be whole numbers in [0, 2^24)";
-      return DT_E_ARG;
-    }
-    if (r[3] < 1.0f) {
-      h->err = row + ": K must be >= 1";
-      return DT_E_ARG;
-    }
-    if (h->n_render_bots > 0)
-      for (int32_t br : h->render_bot_row)
-        if (br == o) {
-          h->err = row + " is a render bot's record (dt_render_bots)";
-          return DT_E_ARG;
-        }
-  }
+  if (const int rc = refused(h, dtrec::walkers<dtrec::Frame>(
+                                    "dt_render_walkers", recs, n, h->n_render_objs,
+                                    h->render_bot_row.data(),
+                                    h->n_render_bots > 0 ? h->render_bot_row.size() : 0)))
+    return rc;
   DevGuard dg(h->device);
-  HIP_OR_FAIL(h, hipDeviceSynchronize());   // launches in flight read the rows
-  if (n > 0) {
-    const size_t rec = DT_RENDER_WALK_STRIDE * sizeof(float);
-    if (!h->render_walk)   // the largest size, once: a captured launch keeps a valid pointer
-      HIP_OR_FAIL(h, hipMalloc(&h->render_walk, DT_MAX_RENDER_OBJECTS * rec));
-    HIP_OR_FAIL(h, hipMemcpy(h->render_walk, recs, (size_t)n * rec, hipMemcpyHostToDevice));
-  }
+  const size_t rec = DT_RENDER_WALK_STRIDE * sizeof(float);
+  UPLOAD_IN_PLACE_OR_FAIL(h, render_walk, DT_MAX_RENDER_OBJECTS * rec, recs, (size_t)n * rec);
   h->n_render_walk = n;
   h->render_walker.assign((size_t)n, 0);
   for (int o = 0; o < n; ++o)
@@ -2569,73 +2486,24 @@ int dt_render_walkers(dt_handle* h, const float* recs, int32_t n) {
 int dt_render_bots(dt_handle* h, const float* recs, const int32_t* render_row, int32_t rows,
                    int32_t n) {
   if (!h) return DT_E_ARG;
-  const int NR = h->n_render_objs;
-  if (n < 0 || n > NR) {
-    h->err = "dt_render_bots: n must be in 0..the count dt_render_objects was given (" +
-             std::to_string(NR) + ")";
-    return DT_E_ARG;
-  }
+  std::vector<int32_t> col;
+  const auto walks = [&](int32_t o) { return h->n_render_walk > 0 && h->render_walker[o]; };
+  if (const int rc = refused(h, dtrec::bots<dtrec::Frame>("dt_render_bots", recs, render_row, rows,
+                                                          n, h->n_render_objs, walks, col)))
+    return rc;
+  DevGuard dg(h->device);
   if (n == 0) {
-    DevGuard dg(h->device);
     HIP_OR_FAIL(h, hipDeviceSynchronize());
     h->n_render_bots = 0;
     return DT_OK;
   }
-  if (!recs || !render_row) {
-    h->err = "dt_render_bots: recs and render_row are required";
-    return DT_E_ARG;
-  }
-  if (rows < 1 || rows > DT_MAX_BOT_ROWS) {
-    h->err = "dt_render_bots: rows must be in 1.." + std::to_string(DT_MAX_BOT_ROWS);
-    return DT_E_ARG;
-  }
-  const size_t bytes = (size_t)rows * n * DT_RENDER_OBJ_STRIDE * sizeof(float);
-  if (bytes > (size_t)DT_MAX_BOT_BYTES) {
-    h->err = "dt_render_bots: the table (" + std::to_string(bytes) + " B) is over " +
-             std::to_string(DT_MAX_BOT_BYTES) + " B";
-    return DT_E_ARG;
-  }
-  std::vector<int32_t> col(DT_MAX_RENDER_OBJECTS, -1);
-  for (int b = 0; b < n; ++b) {
-    const int32_t o = render_row[b];
-    const std::string bot = "dt_render_bots: bot " + std::to_string(b);
-    if (o < 0 || o >= NR) {
-      h->err = bot + ": record " + std::to_string(o) + " is outside dt_render_objects' count";
-      return DT_E_ARG;
-    }
-    if (col[o] >= 0) {
-      h->err = bot + ": record " + std::to_string(o) + " is named twice";
-      return DT_E_ARG;
-    }
-    if (h->n_render_walk > 0 && h->render_walker[o]) {
-      h->err = bot + ": record " + std::to_string(o) + " is a render walker's";
-      return DT_E_ARG;
-    }
-    col[o] = b;
-  }
-  const size_t cnt = (size_t)rows * n * DT_RENDER_OBJ_STRIDE;
-  for (size_t i = 0; i < cnt; ++i)
-    if (!isfinite(recs[i])) {
-      h->err = "dt_render_bots: row " + std::to_string(i / ((size_t)n * DT_RENDER_OBJ_STRIDE)) +
-               " holds a non-finite value";
-      return DT_E_ARG;
-    }
-  DevGuard dg(h->device);
-  void* tab = nullptr;
-  HIP_OR_FAIL(h, hipMalloc(&tab, bytes));
-  hipError_t e = hipMemcpy(tab, recs, bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess && !h->render_bot_col)
-    e = hipMalloc(&h->render_bot_col, DT_MAX_RENDER_OBJECTS * sizeof(int32_t));
-  if (e == hipSuccess) e = hipDeviceSynchronize();   // launches in flight read the old table
-  if (e == hipSuccess)
-    e = hipMemcpy(h->render_bot_col, col.data(), col.size() * sizeof(int32_t),
-                  hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)hipFree(tab);
-    HIP_OR_FAIL(h, e);
-  }
-  if (h->render_bot_tab) (void)hipFree(h->render_bot_tab);
-  h->render_bot_tab = tab;
+  DevBuf tab;
+  if (upload_new(tab, recs, (size_t)rows * n * DT_RENDER_OBJ_STRIDE * sizeof(float),
+                 "hipMalloc(&tab, bytes)", "e", h->err) != hipSuccess ||
+      upload_in_place(h->render_bot_col, col.size() * sizeof(int32_t), col.data(),
+                      col.size() * sizeof(int32_t), {"e", "e", "e"}, h->err) != hipSuccess)
+    return DT_E_HIP;
+  h->render_bot_tab = std::move(tab);
   h->render_bot_rows = rows;
   h->n_render_bots = n;
   h->render_bot_row.assign(render_row, render_row + n);
@@ -2660,12 +2528,7 @@ int dt_render_camera(dt_handle* h, const uint16_t* table, int32_t n) {
       return DT_E_ARG;
     }
   DevGuard dg(h->device);
-  // launches in flight read the table: wait for them (synchronous, as
-  // dt_render_objects); one buffer for the handle's life, so a launch captured
-  // into a graph keeps a valid pointer and reads whatever was uploaded last
-  HIP_OR_FAIL(h, hipDeviceSynchronize());
-  if (!h->render_cam) HIP_OR_FAIL(h, hipMalloc(&h->render_cam, NPIX * sizeof(uint16_t)));
-  HIP_OR_FAIL(h, hipMemcpy(h->render_cam, table, NPIX * sizeof(uint16_t), hipMemcpyHostToDevice));
+  UPLOAD_IN_PLACE_OR_FAIL(h, render_cam, NPIX * sizeof(uint16_t), table, NPIX * sizeof(uint16_t));
   h->render_cam_on = true;
   return DT_OK;
 }
@@ -2677,10 +2540,10 @@ int dt_palette_gray(float* gray8) {
 }
 
 int dt_render_order(dt_handle* h, uint32_t* launches, uint32_t* cost, int32_t* order) {
-  if (!h || !h->render_sched) return DT_E_ARG;
+  if (!h || !h->render_sched.ptr) return DT_E_ARG;
   DevGuard dg(h->device);
   HIP_OR_FAIL(h, hipDeviceSynchronize());
-  const uint32_t* base = (const uint32_t*)h->render_sched;
+  const uint32_t* base = (const uint32_t*)h->render_sched.ptr;
   if (launches) *launches = h->render_launches;
   const size_t n = (size_t)h->n;
   if (cost)

@@ -12,6 +12,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -1182,6 +1183,11 @@ const char* dt_last_error(const dt_handle* h) {
   return h ? h->err.c_str() : g_create_err.c_str();
 }
 
+static int create_failed(const char* hip_call) {
+  g_create_err = hip_call;
+  return DT_E_HIP;
+}
+
 int dt_create(const dt_config* cfg, const dt_map* map, uint64_t seed, int32_t n_envs,
               int32_t device, dt_handle** out) {
   g_create_err.clear();
@@ -1266,7 +1272,8 @@ int dt_create(const dt_config* cfg, const dt_map* map, uint64_t seed, int32_t n_
     return DT_E_ARG;
   }
 
-  dt_handle* h = new dt_handle();
+  std::unique_ptr<dt_handle> own(new dt_handle());
+  dt_handle* h = own.get();
   h->device = device;
   h->n = n_envs;
   h->cfg = *cfg;
@@ -1299,21 +1306,12 @@ int dt_create(const dt_config* cfg, const dt_map* map, uint64_t seed, int32_t n_
   sc.max_spawn_attempts = cfg->max_spawn_attempts;
   sc.reward_scale = cfg->reward_scale;
 
-  int rc = 0;
-  auto fail = [&](const std::string& m) {
-    g_create_err = m;
-    if (h->map_buf) (void)hipFree(h->map_buf);
-    if (h->st_buf) (void)hipFree(h->st_buf);
-    delete h;
-    return DT_E_HIP;
-  };
-  if (hipSetDevice(device) != hipSuccess) return fail("hipSetDevice failed");
+  if (hipSetDevice(device) != hipSuccess) return create_failed("hipSetDevice failed");
   // map image: curve records | objects | spawn objects | curve_start (u16) | kind |
   // drivable
   const size_t lds = dt::map_lds_bytes(T, (int)drv.size(), C, NO, NS);
   if (lds > dt::kMaxMapLdsBytes) {
     g_create_err = "dt_create: map image over the LDS budget (" + std::to_string(lds) + " B)";
-    delete h;
     return DT_E_ARG;
   }
   std::vector<uint16_t> cs(T + 1);
@@ -1325,9 +1323,9 @@ int dt_create(const dt_config* cfg, const dt_map* map, uint64_t seed, int32_t n_
   // (behind the drivable list: room for dt_set_walkers' rows and dt_set_bots'
   // header, dt::walk_rows)
   const size_t wb = ((size_t)NO * dt::kWalkRec + dt::kBotHdr) * 8;
-  if (hipMalloc(&h->map_buf, cb + ob + spb + sb16 + kb + db + wb) != hipSuccess)
-    return fail("hipMalloc(map)");
-  char* mb = (char*)h->map_buf;
+  if (h->map_buf.alloc(cb + ob + spb + sb16 + kb + db + wb) != hipSuccess)
+    return create_failed("hipMalloc(map)");
+  char* mb = (char*)h->map_buf.ptr;
   char* m_cs = mb + cb + ob + spb;
   if ((cb && hipMemcpy(mb, rec.data(), cb, hipMemcpyHostToDevice) != hipSuccess) ||
       (ob && hipMemcpy(mb + cb, map->objects, ob, hipMemcpyHostToDevice) != hipSuccess) ||
@@ -1337,7 +1335,7 @@ int dt_create(const dt_config* cfg, const dt_map* map, uint64_t seed, int32_t n_
       hipMemcpy(m_cs + sb16, map->kind, (size_t)T, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(m_cs + sb16 + kb, drv.data(), drv.size() * 2, hipMemcpyHostToDevice) !=
           hipSuccess)
-    return fail("hipMemcpy(map)");
+    return create_failed("hipMemcpy(map)");
   h->map.width = map->width;
   h->map.height = map->height;
   h->map.n_tiles = T;
@@ -1360,9 +1358,9 @@ int dt_create(const dt_config* cfg, const dt_map* map, uint64_t seed, int32_t n_
   const size_t spawn_at = 4 * N8 + 3 * N4 + 512;
   const size_t R = (size_t)dt::kSlotRec;
   const size_t total = spawn_at + (R + 1) * S * N8 + 2 * N4;
-  if (hipMalloc(&h->st_buf, total) != hipSuccess) return fail("hipMalloc(state)");
-  if (hipMemset(h->st_buf, 0, total) != hipSuccess) return fail("hipMemset(state)");
-  char* sb = (char*)h->st_buf;
+  if (h->st_buf.alloc(total) != hipSuccess) return create_failed("hipMalloc(state)");
+  if (hipMemset(h->st_buf.ptr, 0, total) != hipSuccess) return create_failed("hipMemset(state)");
+  char* sb = (char*)h->st_buf.ptr;
   h->st.x = (double*)sb;
   h->st.z = (double*)(sb + N8);
   h->st.angle = (double*)(sb + 2 * N8);
@@ -1376,26 +1374,20 @@ int dt_create(const dt_config* cfg, const dt_map* map, uint64_t seed, int32_t n_
   h->st.pre_key = (uint64_t*)(sb + spawn_at + R * S * N8);
   h->st.want = (uint32_t*)(sb + spawn_at + (R + 1) * S * N8);
   h->st.tick = (uint32_t*)(sb + spawn_at + (R + 1) * S * N8 + N4);
-  *out = h;
-  rc = dt_render_init(h, map);
+  int rc = dt_render_init(h, map);
   if (rc == DT_OK) rc = dt_seed(h, nullptr, seed, 0);
   if (rc) {
-    std::string m = h->err;
-    dt_destroy(h);
     *out = nullptr;
-    g_create_err = m;
+    g_create_err = h->err;
     return rc;
   }
+  *out = own.release();
   return DT_OK;
 }
 
 int dt_destroy(dt_handle* h) {
   if (!h) return DT_E_ARG;
   (void)hipSetDevice(h->device);
-  dt_render_free(h);
-  if (h->bot_tab) (void)hipFree(h->bot_tab);
-  if (h->map_buf) (void)hipFree(h->map_buf);
-  if (h->st_buf) (void)hipFree(h->st_buf);
   delete h;
   return DT_OK;
 }
@@ -1462,61 +1454,17 @@ static decltype(&step_kernel<false>) step_kernel_of(const dt_handle* h) {
   return h->map.n_walk > 0 ? step_kernel<true> : step_kernel<false>;
 }
 
-// A walker value that must be a whole number of steps in [0, 2^24).
-static bool walk_steps_ok(double v) { return v >= 0.0 && v < 16777216.0 && v == floor(v); }
+static_assert(dtrec::kWalkPacked == dt::kWalkRec, "dtrecords.h packs the rows the kernels read");
 
 int dt_set_walkers(dt_handle* h, const double* recs, int32_t n) {
   if (!h) return DT_E_ARG;
-  const int NO = h->map.n_obj;
-  if (n != 0 && n != NO) {
-    h->err = "dt_set_walkers: n must be 0 or the handle's n_objects (" + std::to_string(NO) + ")";
-    return DT_E_ARG;
-  }
-  if (n > 0 && !recs) {
-    h->err = "dt_set_walkers: recs is null";
-    return DT_E_ARG;
-  }
-  std::vector<double> rows((size_t)n * dt::kWalkRec, 0.0);
-  for (int o = 0; o < n; ++o) {
-    const double* r = recs + (size_t)o * DT_WALK_STRIDE;
-    const std::string row = "dt_set_walkers: row " + std::to_string(o);
-    bool zero = true;
-    for (int i = 0; i < DT_WALK_STRIDE; ++i) {
-      if (!isfinite(r[i])) {
-        h->err = row + " holds a non-finite value";
-        return DT_E_ARG;
-      }
-      zero = zero && r[i] == 0.0;
-    }
-    if (zero) continue;   // a static object
-    if (!(r[2] > 0.0)) {
-      h->err = row + ": vel must be > 0";
-      return DT_E_ARG;
-    }
-    if (!walk_steps_ok(r[3]) || !walk_steps_ok(r[4])) {
-      h->err = row + ": W and K must be whole numbers in [0, 2^24)";
-      return DT_E_ARG;
-    }
-    if (r[4] < 1.0) {
-      h->err = row + ": K must be >= 1";
-      return DT_E_ARG;
-    }
-    double* d = rows.data() + (size_t)o * dt::kWalkRec;
-    d[0] = r[0];
-    d[1] = r[1];
-    d[2] = r[2];
-    const uint64_t wk = (uint64_t)(uint32_t)r[3] | ((uint64_t)(uint32_t)r[4] << 32);
-    memcpy(d + 3, &wk, 8);
-    for (int32_t br : h->bot_row)
-      if (br == o) {
-        h->err = row + " is a bot's row (dt_set_bots)";
-        return DT_E_ARG;
-      }
-  }
-  const int rc = set_movers(h, "dt_set_walkers", rows, h->bot_row, h->bot_tab, h->bot_rows);
-  if (rc != DT_OK) return rc;
-  h->walk_rows_host = rows;
-  return DT_OK;
+  std::vector<double> rows;
+  int rc = refused(h, dtrec::walkers<dtrec::Step>("dt_set_walkers", recs, n, h->map.n_obj,
+                                                  h->bot_row.data(), h->bot_row.size(), &rows));
+  if (rc == DT_OK)
+    rc = set_movers(h, "dt_set_walkers", rows, h->bot_row, h->bot_tab.ptr, h->bot_rows);
+  if (rc == DT_OK) h->walk_rows_host = rows;
+  return rc;
 }
 
 int dt_bot_path(dt_handle* h, const double* home, const double* params, int32_t n, int32_t rows,
@@ -1553,8 +1501,11 @@ int dt_bot_path(dt_handle* h, const double* home, const double* params, int32_t 
   DevGuard dg(h->device);
   const size_t pb = (size_t)rows * n * 3 * sizeof(double), qb = (size_t)n * DT_BOT_STRIDE * 8,
                sb = (size_t)n * 2 * sizeof(int32_t);
-  char* buf = nullptr;   // path | params | status
-  HIP_OR_FAIL(h, hipMalloc((void**)&buf, pb + qb + sb));
+  DevBuf scratch;   // path | params | status
+  if (hip_said(h->err, "hipMalloc((void**)&buf, pb + qb + sb)", scratch.alloc(pb + qb + sb)) !=
+      hipSuccess)
+    return DT_E_HIP;
+  char* buf = (char*)scratch.ptr;
   double* d_path = (double*)buf;
   double* d_par = (double*)(buf + pb);
   int32_t* d_st = (int32_t*)(buf + pb + qb);
@@ -1591,81 +1542,30 @@ int dt_bot_path(dt_handle* h, const double* home, const double* params, int32_t 
     h->err = "dt_bot_path: hipMemcpy(path) failed";
     rc = DT_E_HIP;
   }
-  (void)hipFree(buf);
   return rc;
 }
 
 int dt_set_bots(dt_handle* h, const double* recs, const int32_t* object_row, int32_t rows,
                 int32_t n) {
   if (!h) return DT_E_ARG;
-  const int NO = h->map.n_obj;
-  if (n < 0 || n > NO) {
-    h->err = "dt_set_bots: n must be in 0..n_objects (" + std::to_string(NO) + ")";
-    return DT_E_ARG;
-  }
-  std::vector<int32_t> bot_row;
-  void* tab = nullptr;
+  std::vector<int32_t> col;
+  const auto walks = [&](int32_t o) { return dtrec::packed_walks(h->walk_rows_host, o); };
+  int rc = refused(h, dtrec::bots<dtrec::Step>("dt_set_bots", recs, object_row, rows, n,
+                                               h->map.n_obj, walks, col));
+  if (rc != DT_OK) return rc;
+  const std::vector<int32_t> bot_row(object_row, object_row + n);
+  DevBuf tab;
   if (n > 0) {
-    if (!recs || !object_row) {
-      h->err = "dt_set_bots: recs and object_row are required";
-      return DT_E_ARG;
-    }
-    if (rows < 1 || rows > DT_MAX_BOT_ROWS) {
-      h->err = "dt_set_bots: rows must be in 1.." + std::to_string(DT_MAX_BOT_ROWS);
-      return DT_E_ARG;
-    }
-    const size_t bytes = (size_t)rows * n * DT_OBJ_STRIDE * sizeof(double);
-    if (bytes > (size_t)DT_MAX_BOT_BYTES) {
-      h->err = "dt_set_bots: the table (" + std::to_string(bytes) + " B) is over " +
-               std::to_string(DT_MAX_BOT_BYTES) + " B";
-      return DT_E_ARG;
-    }
-    for (int b = 0; b < n; ++b) {
-      const int32_t o = object_row[b];
-      const std::string bot = "dt_set_bots: bot " + std::to_string(b);
-      if (o < 0 || o >= NO) {
-        h->err = bot + ": row " + std::to_string(o) + " is outside n_objects";
-        return DT_E_ARG;
-      }
-      for (int c = 0; c < b; ++c)
-        if (object_row[c] == o) {
-          h->err = bot + ": row " + std::to_string(o) + " is named twice";
-          return DT_E_ARG;
-        }
-      if (!h->walk_rows_host.empty()) {
-        uint64_t wk;
-        memcpy(&wk, h->walk_rows_host.data() + (size_t)o * dt::kWalkRec + 3, 8);
-        if ((uint32_t)(wk >> 32) != 0u) {
-          h->err = bot + ": row " + std::to_string(o) + " is a walker's row (dt_set_walkers)";
-          return DT_E_ARG;
-        }
-      }
-    }
-    const size_t cnt = (size_t)rows * n * DT_OBJ_STRIDE;
-    for (size_t i = 0; i < cnt; ++i)
-      if (!isfinite(recs[i])) {
-        h->err = "dt_set_bots: row " + std::to_string(i / ((size_t)n * DT_OBJ_STRIDE)) +
-                 " holds a non-finite value";
-        return DT_E_ARG;
-      }
-    bot_row.assign(object_row, object_row + n);
     DevGuard dg(h->device);
-    HIP_OR_FAIL(h, hipMalloc(&tab, bytes));
-    const hipError_t e = hipMemcpy(tab, recs, bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      (void)hipFree(tab);
-      HIP_OR_FAIL(h, e);
-    }
+    if (upload_new(tab, recs, (size_t)rows * n * DT_OBJ_STRIDE * sizeof(double),
+                   "hipMalloc(&tab, bytes)", "e", h->err) != hipSuccess)
+      return DT_E_HIP;
   }
   // (the kernels read the table's address from the header set_movers uploads,
   // not from a launch argument: a captured graph follows a new table)
-  const int rc = set_movers(h, "dt_set_bots", h->walk_rows_host, bot_row, tab, rows);
-  if (rc != DT_OK) {
-    if (tab) (void)hipFree(tab);
-    return rc;
-  }
-  if (h->bot_tab) (void)hipFree(h->bot_tab);   // set_movers waited for the device
-  h->bot_tab = tab;
+  rc = set_movers(h, "dt_set_bots", h->walk_rows_host, bot_row, tab.ptr, rows);
+  if (rc != DT_OK) return rc;
+  h->bot_tab = std::move(tab);
   h->bot_rows = n > 0 ? rows : 0;
   h->bot_row = bot_row;
   return DT_OK;
