@@ -174,11 +174,22 @@ def _merge_waves(cnt, mean, m2):
 
 
 def twopass32(v, gamma, beta, eps, waves=4):
-    """conv4's epilogue (kOut 2) in float32: per wave the sum and then the M2
-    about its mean by xor butterflies (16, 8, .., 1), the waves merged in
-    order, sc = gamma / sqrt(M2 / pixels + eps), out = v sc + (beta - mean sc).
-    v [P, C, pixels] float32; returns float32 [P, C, pixels] before the fp16
-    rounding of the store."""
+    """conv4's epilogue (kOut 2) in float32: the two-pass statistics
+    (twopass_stats32), sc = gamma / sqrt(M2 / pixels + eps), out = v sc +
+    (beta - mean sc).  v [P, C, pixels] float32; returns float32 [P, C,
+    pixels] before the fp16 rounding of the store."""
+    f = np.float32
+    v = np.asarray(v, dtype=f)
+    mu, mm = twopass_stats32(v, waves)
+    sc = gamma.astype(f) / np.sqrt(mm / f(v.shape[-1]) + f(eps))
+    sh = beta.astype(f) - mu * sc
+    return v * sc[..., None] + sh[..., None]
+
+
+def twopass_stats32(v, waves=4):
+    """conv4's two-pass statistics in float32: per wave the sum and then the
+    M2 about its mean by xor butterflies (16, 8, .., 1), the waves merged in
+    order.  v [P, C, pixels] float32; returns (mean, M2) float32 [P, C]."""
     f = np.float32
     v = np.asarray(v, dtype=f)
     pn, ch, npix = v.shape
@@ -197,10 +208,7 @@ def twopass32(v, gamma, beta, eps, waves=4):
     mean_w = butterfly(np.where(valid, vp, f(0))) * inw[:, None]
     dd = np.where(valid, vp - mean_w, f(0))
     m2_w = butterfly(dd * dd)
-    mu, mm = _merge_waves(nw, mean_w[..., 0], m2_w[..., 0])
-    sc = gamma.astype(f) / np.sqrt(mm / f(npix) + f(eps))
-    sh = beta.astype(f) - mu * sc
-    return v * sc[..., None] + sh[..., None]
+    return _merge_waves(nw, mean_w[..., 0], m2_w[..., 0])
 
 
 def _stats64(d):
