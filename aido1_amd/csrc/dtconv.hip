@@ -56,11 +56,6 @@ __device__ unsigned long long g_c1stamps[8 * 2 * 48 * 8];
 #ifndef DTCONV1_BDEPTH
 #define DTCONV1_BDEPTH 2
 #endif
-// conv1s_kernel's reduction layout: 1 = K 192 (3-channel pixels, 12 MFMAs a
-// tile), 0 = K 256 (4-channel pixels with a zero channel, 16 MFMAs a tile)
-#ifndef DTCONV1_K192
-#define DTCONV1_K192 1
-#endif
 // conv1s_kernel: resident workgroups a CU of the persistent grid; 0 = as many
 // as the occupancy allows (diagnostic builds fix it)
 #ifndef DTCONV1_PER
@@ -73,7 +68,7 @@ using namespace dtconv;
 using namespace dtconv::c1;
 
 // One pixel's 32 channels as fp16 NHWC from a 32x32x16 MFMA tile (lane = pixel
-// column, register r = channel (r&3) + 8*(r>>2) + 4h): v_permlane32_swap pairs
+// column, register r = channel (r&3) + 8*(r>>2) + 4h): swap_halves pairs
 // the two half-waves' 4-channel groups, so each lane stores two 16-B chunks
 // (channels 16m + 8h .. +7 at byte 32m + 16h) instead of four 8-B ones.
 // `sample` is the sample's first element (wave-uniform), `px` the lane's pixel.
@@ -94,14 +89,7 @@ __device__ __forceinline__ void store_px32(__half* sample, int px, const float (
     u[q][0] = *reinterpret_cast<const uint32_t*>(&v0);
     u[q][1] = *reinterpret_cast<const uint32_t*>(&v1);
   }
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const auto r = __builtin_amdgcn_permlane32_swap(u[2 * m][e], u[2 * m + 1][e], false, false);
-      u[2 * m][e] = r[0];
-      u[2 * m + 1][e] = r[1];
-    }
+  swap_halves(u);
   const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(sample), 0, kBytes,
                                                       0x00020000);
   const int off = valid ? px * 64 + 16 * h : kBytes;
@@ -123,26 +111,12 @@ __device__ __forceinline__ void store_px32(__half* sample, int px, const float (
 // per CU, so one's barrier leaves the other's MFMAs running.  Reference mode:
 // per-lane Welford statistics over the sample, merged (Chan) into ONE
 // (mean, M2) per sample and channel.
-constexpr bool kK192 = DTCONV1_K192 != 0;
-constexpr int kSPxB = kK192 ? 6 : 8;                    // bytes a ring pixel: fp16 x 3 (x 4)
-constexpr int kSRowB = IW * kSPxB;                      // 960 (1280) B
-constexpr int kSMfma = kK192 ? 12 : 16;                 // MFMAs a tile
-constexpr int kSGrp = kK192 ? 3 : 4;                    // MFMAs a B-fragment group
 #ifdef DTCONV_CHECK
 // Bounds-checked diagnostic build (tests/test_gpu_actor.py): every frame-ring
-// load of conv1s_kernel checks its float4 against the n x slots x 120 x 160
-// ring and sets this word when it would read past it (round 2 fixed such a
-// read on the last sample's row-free step).
+// load of conv1s_kernel checks its 4 elements against the n x slots x 120 x
+// 160 ring and sets this word when it would read past it (round 2 fixed such
+// a read on the last sample's row-free step).
 __device__ unsigned int g_conv1_oob;
-#define CONV1_CHECK(p)                                                          \
-  do {                                                                          \
-    const size_t e_ = (size_t)((p) - ringT);                                    \
-    if (e_ + 4 > (size_t)n * (size_t)slots * plane) atomicOr(&g_conv1_oob, 1u); \
-  } while (0)
-#else
-#define CONV1_CHECK(p) \
-  do {                 \
-  } while (0)
 #endif
 
 // kIdx: the ring holds palette-index frames (u8, dt_render_io.index): a load
@@ -154,9 +128,8 @@ __global__ void __launch_bounds__(kSThreads, 2)   // 2 waves / SIMD: <= 256 regi
 conv1s_kernel(int n, const void* __restrict__ ring, int slots, int s0, int s1, int s2,
               const half8* __restrict__ wfrag, const float* __restrict__ bias,
               __half* __restrict__ y, float* __restrict__ partials, float slope, WeightSplit ws) {
-  using Elem = typename std::conditional<kIdx, uint8_t, float>::type;
-  using Item = typename std::conditional<kIdx, uint32_t, float4>::type;
-  const Elem* __restrict__ ringT = static_cast<const Elem*>(ring);
+  using Item = c1::Item<kIdx>;
+  const Elem<kIdx>* __restrict__ ringT = static_cast<const Elem<kIdx>*>(ring);
   __shared__ __attribute__((aligned(16))) unsigned char rb[kSRing * kSRowB];
   __shared__ float s_gray[8];
   __shared__ float red[kSW][CO][3];
@@ -173,40 +146,16 @@ conv1s_kernel(int n, const void* __restrict__ ring, int slots, int s0, int s1, i
   const int total = sp.my * kSSteps;
   if (total == 0) return;
   auto sample = [&](int k) __attribute__((always_inline)) { return sp.sbeg + sp.bid + k * sp.gdim; };
-  const size_t plane = (size_t)IH * IW;
-
-  // a thread's load items are fixed (row r_i, quad qq_i of the step's range);
-  // only the range start and length change per step
-  int it_r[kSPre], it_off[kSPre], it_lds[kSPre];
-#pragma unroll
-  for (int i = 0; i < kSPre; ++i) {
-    const int q = tid + i * kSThreads;
-    it_r[i] = q / kSQuads;
-    it_off[i] = it_r[i] * IW + 4 * (q - it_r[i] * kSQuads);
-    it_lds[i] = 4 * kSPxB * (q - it_r[i] * kSQuads);
-  }
-  // rows r0..r1 of the k-th sample into registers, one float4 per stacked
-  // frame; every load issued on every path (items past the range re-load the
-  // range's first quad, the sample is clamped), so the compiler's vmcnt waits
-  // stay exact.  A step may add no rows (r0 = r1 + 1, up to IH at the end of a
-  // sample): its loads then read the sample's row 0, never past the plane.
+  const Items its = items(tid);
+#ifdef DTCONV_CHECK
+  auto check = [&](const Elem<kIdx>* p) __attribute__((always_inline)) {
+    if ((size_t)(p - ringT) + 4 > (size_t)n * (size_t)slots * IH * IW) atomicOr(&g_conv1_oob, 1u);
+  };
+#else
+  const NoCheck check;
+#endif
   auto issue = [&](Item (&pre)[kSPre][3], int k, int r0, int r1) __attribute__((always_inline)) {
-    const int rows = r1 - r0 + 1;
-    const int ns = sample(k) < send ? sample(k) : send - 1;
-    const Elem* base = ringT + (size_t)ns * slots * plane + (size_t)(rows > 0 ? r0 : 0) * IW;
-    const Elem* p0 = base + (size_t)s0 * plane;
-    const Elem* p1 = base + (size_t)s1 * plane;
-    const Elem* p2 = base + (size_t)s2 * plane;
-#pragma unroll
-    for (int i = 0; i < kSPre; ++i) {
-      const int off = it_r[i] < rows ? it_off[i] : 0;
-      CONV1_CHECK(p0 + off);
-      CONV1_CHECK(p1 + off);
-      CONV1_CHECK(p2 + off);
-      pre[i][0] = *reinterpret_cast<const Item*>(p0 + off);
-      pre[i][1] = *reinterpret_cast<const Item*>(p1 + off);
-      pre[i][2] = *reinterpret_cast<const Item*>(p2 + off);
-    }
+    c1::issue<kIdx>(pre, its, ringT, slots, s0, s1, s2, sample(k), send, r0, r1, check);
   };
   // a load item's 4 pixels of one frame as grey floats
   auto px4 = [&](const Item& it, float (&o)[4]) __attribute__((always_inline)) {
@@ -220,68 +169,36 @@ conv1s_kernel(int n, const void* __restrict__ ring, int slots, int s0, int s1, i
       o[3] = it.w;
     }
   };
-  // fp16 4-channel pixels (channel 3 = 0) into the ring: row R of the stream
-  // (k * IH + r) sits in slot R % kSRing
+  // fp16 3-channel pixels into the ring: row R of the stream (k * IH + r)
+  // sits in slot R % kSRing
   auto commit = [&](const Item (&pre)[kSPre][3], int k, int r0, int r1) __attribute__((always_inline)) {
     const int rows = r1 - r0 + 1;
 #pragma unroll
     for (int i = 0; i < kSPre; ++i) {
-      if (it_r[i] >= rows) continue;
-      const int slot = (k * IH + r0 + it_r[i]) & (kSRing - 1);
+      if (its.r[i] >= rows) continue;
+      const int slot = (k * IH + r0 + its.r[i]) & (kSRing - 1);
       float av[4], bv[4], cv[4];
       px4(pre[i][0], av);
       px4(pre[i][1], bv);
       px4(pre[i][2], cv);
-      if constexpr (kK192) {
-        // 4 pixels x 3 channels, pixel-major: (a0 b0)(c0 a1)(b1 c1)(a2 b2)(c2 a3)(b3 c3)
-        const float f[12] = {av[0], bv[0], cv[0], av[1], bv[1], cv[1],
-                             av[2], bv[2], cv[2], av[3], bv[3], cv[3]};
-        uint32_t u[6];
+      // 4 pixels x 3 channels, pixel-major: (a0 b0)(c0 a1)(b1 c1)(a2 b2)(c2 a3)(b3 c3)
+      const float f[12] = {av[0], bv[0], cv[0], av[1], bv[1], cv[1],
+                           av[2], bv[2], cv[2], av[3], bv[3], cv[3]};
+      uint32_t u[6];
 #pragma unroll
-        for (int e = 0; e < 6; ++e) {
-          const __half2 hv = __floats2half2_rn(f[2 * e], f[2 * e + 1]);
-          u[e] = *reinterpret_cast<const uint32_t*>(&hv);
-        }
-        uint2* dst = reinterpret_cast<uint2*>(rb + slot * kSRowB + it_lds[i]);   // 8-B aligned
-        dst[0] = make_uint2(u[0], u[1]);
-        dst[1] = make_uint2(u[2], u[3]);
-        dst[2] = make_uint2(u[4], u[5]);
-      } else {
-        uint32_t u[8];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const __half2 lo = __floats2half2_rn(av[e], bv[e]);
-          const __half2 hi = __floats2half2_rn(cv[e], 0.0f);
-          u[2 * e] = *reinterpret_cast<const uint32_t*>(&lo);
-          u[2 * e + 1] = *reinterpret_cast<const uint32_t*>(&hi);
-        }
-        u32x4* dst = reinterpret_cast<u32x4*>(rb + slot * kSRowB + it_lds[i]);
-        dst[0] = u32x4{u[0], u[1], u[2], u[3]};
-        dst[1] = u32x4{u[4], u[5], u[6], u[7]};
+      for (int e = 0; e < 6; ++e) {
+        const __half2 hv = __floats2half2_rn(f[2 * e], f[2 * e + 1]);
+        u[e] = *reinterpret_cast<const uint32_t*>(&hv);
       }
+      uint2* dst = reinterpret_cast<uint2*>(rb + slot * kSRowB + its.lds[i]);   // 8-B aligned
+      dst[0] = make_uint2(u[0], u[1]);
+      dst[1] = make_uint2(u[2], u[3]);
+      dst[2] = make_uint2(u[4], u[5]);
     }
   };
 
-  // A fragments.  K 192: MFMA s covers kernel rows ky = 2(s/3) + h (h = the
-  // lane half) and 8 of the 24 (kx, c) values of a row, t = 8(s%3) + j ->
-  // kx = t/3, c = t%3: a lane's 8 k are 16 contiguous bytes of a ring row.
-  // Gathered once from the dt_conv1 fragment layout (include/dtactor.h).
   half8 wa[kSMfma];
-  if constexpr (kK192) {
-    const _Float16* wh = reinterpret_cast<const _Float16*>(wfrag);
-    const int co = lane & 31, hh = lane >> 5;
-#pragma unroll
-    for (int s = 0; s < kSMfma; ++s)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int ky = 2 * (s / 3) + hh, t = 8 * (s % 3) + e, kx = t / 3, c = t % 3;
-        const int s1 = 2 * ky + kx / 4, l1 = co + 32 * ((kx & 3) >> 1), j1 = 4 * (kx & 1) + c;
-        wa[s][e] = wh[(s1 * 64 + l1) * 8 + j1];
-      }
-  } else {
-#pragma unroll
-    for (int s = 0; s < kSMfma; ++s) wa[s] = wfrag[s * 64 + lane];
-  }
+  gather_a(wa, reinterpret_cast<const _Float16*>(wfrag));
   if (tid < CO) s_bias[tid] = bias[tid];
   if (kIdx && tid < 8) s_gray[tid] = dr::kPalGray[tid];
   float w_cnt = 0.0f, w_mean[16], w_m2[16];
@@ -290,19 +207,15 @@ conv1s_kernel(int n, const void* __restrict__ ring, int slots, int s0, int s1, i
 
   auto step = [&](int g, int k, int j, Item (&nxt)[kSPre][3], const Item (&cur)[kSPre][3]) __attribute__((always_inline)) {
     const int ns = sample(k);
-    const bool last_j = j + 1 == kSSteps;
-    const int k1 = last_j ? k + 1 : k, j1 = last_j ? 0 : j + 1;   // step g+1
-    const int k2 = (j1 + 1 == kSSteps) ? k1 + 1 : k1;             // step g+2
+    const StepIdx si = step_idx<Stream>(k, j);
     C1STAMP(0);
-    if (!(DTCONV_SKIP & 1)) issue(nxt, k2, s_first_new(j1), s_last_new(j1));
+    if (!(DTCONV_SKIP & 1)) issue(nxt, si.k2, Stream::first_new(si.j1), Stream::last_new(si.j1));
 
-    const int t = kSW * j + wave;
-    const int p = 32 * t + col;
-    const bool valid = p < kSPix;
-    const int pc = valid ? p : 0;
-    const int oy = pc / OW, ox = pc - oy * OW;
-    const int rbase = k * IH + 2 * oy;
-    const int cx = kK192 ? 12 * ox : (2 * ox + 2 * h) * 8;
+    const TileIdx ti = tile_idx<Stream>(j, wave, col);
+    const bool valid = ti.valid;
+    const int pc = ti.pc;
+    const int rbase = k * IH + 2 * ti.oy;
+    const int cx = 12 * ti.ox;
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = s_bias[(r & 3) + 8 * (r >> 2) + 4 * h];
@@ -312,17 +225,11 @@ conv1s_kernel(int n, const void* __restrict__ ring, int slots, int s0, int s1, i
     half8 bq[kBD][kSGrp];
     auto ld = [&](half8 (&b)[kSGrp], int gy) __attribute__((always_inline)) {
 #pragma unroll
-      for (int i = 0; i < kSGrp; ++i) {
-        if constexpr (kK192) {   // row 2gy + h, bytes 12 ox + 16 i: 4-B aligned
-          using u32x4a = __attribute__((ext_vector_type(4), aligned(4))) uint32_t;
-          const int off = ((rbase + 2 * gy + h) & (kSRing - 1)) * kSRowB + cx + 16 * i;
-          const u32x4a w = *reinterpret_cast<const u32x4a*>(rb + off);
-          b[i] = __builtin_bit_cast(half8, w);
-        } else {
-          const int ky = 2 * gy + (i >> 1), kx0 = (i & 1) * 4;
-          const int off = ((rbase + ky) & (kSRing - 1)) * kSRowB + cx + kx0 * 8;
-          b[i] = *reinterpret_cast<const half8*>(rb + off);
-        }
+      for (int i = 0; i < kSGrp; ++i) {   // row 2gy + h, bytes 12 ox + 16 i: 4-B aligned
+        using u32x4a = __attribute__((ext_vector_type(4), aligned(4))) uint32_t;
+        const int off = ((rbase + 2 * gy + h) & (kSRing - 1)) * kSRowB + cx + 16 * i;
+        const u32x4a w = *reinterpret_cast<const u32x4a*>(rb + off);
+        b[i] = __builtin_bit_cast(half8, w);
       }
     };
     if (DTCONV_SKIP & 32) {   // diagnostic: MFMAs on fragments not read from LDS
@@ -351,64 +258,15 @@ conv1s_kernel(int n, const void* __restrict__ ring, int slots, int s0, int s1, i
     if (kStats) centre_px32(v, s_c, j == 0 && wave == 0 && col == 0, j == 0, h);
     if (!(DTCONV_SKIP & 4)) store_px32<kSPix>(y + (size_t)ns * kSPix * CO, pc, v, h, valid);
     if (kStats && !(DTCONV_SKIP & 8)) {
-      if (valid) {   // Welford over this lane's pixels
-        w_cnt += 1.0f;
-        const float inv = __builtin_amdgcn_rcpf(w_cnt);   // 1 ulp: an O(1e-7) relative weight error
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float d = v[r] - w_mean[r];
-          w_mean[r] += d * inv;
-          w_m2[r] += d * (v[r] - w_mean[r]);
-        }
-      }
-      if (last_j) {   // the 32 lanes of each half (same 16 channels), then the waves
-#pragma unroll
-        for (int o = 1; o < 32; o <<= 1) {
-          const float nb = __shfl_xor(w_cnt, o, 32);
-          const float tot = w_cnt + nb;
-          const float fa = tot > 0.0f ? nb / tot : 0.0f, fb = tot > 0.0f ? w_cnt * nb / tot : 0.0f;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const float mb = __shfl_xor(w_mean[r], o, 32), m2b = __shfl_xor(w_m2[r], o, 32);
-            const float d = mb - w_mean[r];
-            w_mean[r] += d * fa;
-            w_m2[r] += m2b + d * d * fb;
-          }
-          w_cnt = tot;
-        }
-        if (col == 0)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int c = (r & 3) + 8 * (r >> 2) + 4 * h;
-            red[wave][c][0] = w_cnt;
-            red[wave][c][1] = w_mean[r];
-            red[wave][c][2] = w_m2[r];
-          }
-        __syncthreads();
-        if (tid < CO) {
-          float cnt = 0.0f, mean = 0.0f, m2 = 0.0f;
-          for (int w = 0; w < kSW; ++w) {
-            const float nb = red[w][tid][0];
-            if (nb <= 0.0f) continue;
-            const float tot = cnt + nb, d = red[w][tid][1] - mean;
-            mean += d * (nb / tot);
-            m2 += red[w][tid][2] + d * d * (cnt * nb / tot);
-            cnt = tot;
-          }
-          float* pp = partials + ((size_t)ns * CO + tid) * 3;
-          pp[0] = mean;
-          pp[1] = m2;
-          pp[2] = s_c[tid];
-        }
-        w_cnt = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) w_mean[r] = w_m2[r] = 0.0f;
-      }
+      if (valid) welford_add<true>(v, w_cnt, w_mean, w_m2);   // over this lane's pixels
+      if (si.last_j)
+        stats_flush<kSW>(w_cnt, w_mean, w_m2, red, s_c, partials + (size_t)ns * CO * 3, tid, wave,
+                         col, h);
     }
     // step g+1's rows into the ring: their slots hold rows no wave reads in
     // this step; the barrier publishes them for the next
     C1STAMP(3);
-    if (g + 1 < total && !(DTCONV_SKIP & 16)) commit(cur, k1, s_first_new(j), s_last_new(j));
+    if (g + 1 < total && !(DTCONV_SKIP & 16)) commit(cur, si.k1, Stream::first_new(j), Stream::last_new(j));
     C1STAMP(4);
     __syncthreads();
     C1STAMP(5);
@@ -416,25 +274,17 @@ conv1s_kernel(int n, const void* __restrict__ ring, int slots, int s0, int s1, i
 
   // prologue: step 0's rows into the ring, step 1's into registers
   Item pa[kSPre][3], pb[kSPre][3];
-  issue(pa, 0, 0, s_hi(0));
+  issue(pa, 0, 0, Stream::hi(0));
   if (kIdx) __syncthreads();   // s_gray
-  commit(pa, 0, 0, s_hi(0));
-  if (total > 1) issue(pb, kSSteps == 1 ? 1 : 0, s_first_new(0), s_last_new(0));
+  commit(pa, 0, 0, Stream::hi(0));
+  if (total > 1) issue(pb, kSSteps == 1 ? 1 : 0, Stream::first_new(0), Stream::last_new(0));
   __syncthreads();
   // drain the prologue's loads: they land in other registers than the loop's
   // prefetch sets, and without this the compiler's wait analysis merges that
   // state into the loop header and waits for the previous step's prefetch
   // before every step's MFMAs (instead of at the commit that reads it)
   __builtin_amdgcn_s_waitcnt(0);
-  int k = 0, j = 0;
-  for (int g = 0; g < total; g += 2) {
-    step(g, k, j, pa, pb);
-    if (++j == kSSteps) { j = 0; ++k; }
-    if (g + 1 < total) {
-      step(g + 1, k, j, pb, pa);
-      if (++j == kSSteps) { j = 0; ++k; }
-    }
-  }
+  run_steps<kSSteps>(total, pa, pb, step);
 }
 
 // Reference mode: y = (y - mean) / sqrt(var + eps) * gamma + beta in place from
@@ -482,7 +332,7 @@ conv1_norm_kernel(__half* __restrict__ y, const float* __restrict__ partials,
 // epilogue is done: one barrier per step, HBM loads overlapped with compute.
 //
 //   ring  input row r of the WG's k-th sample lives in slot (k*IH + r) % kRing
-//         (ConvGeom::ring() rows: a step's rows plus its successor's); a row is
+//         (RowStream::ring() rows: a step's rows plus its successor's); a row is
 //         IW pixels x 64 B, stride-2 layers store the even then the odd
 //         columns (a lane's neighbour reads the next pixel of the same plane),
 //         and chunk c (8 channels) of the pixel at position pos sits at
@@ -500,45 +350,6 @@ conv1_norm_kernel(__half* __restrict__ y, const float* __restrict__ partials,
 //         statistics over the registers, BatchNorm, written flattened in NCHW
 //         order (the reference's view(x.size(0), -1)) for the first linear;
 //         3: flattened, no norm
-template <int IH, int IW, int OH, int OW, int ST, int NW>
-struct ConvGeom {
-  static constexpr int kPix = OH * OW;
-  static constexpr int kTiles = (kPix + 31) / 32;
-  static constexpr int kSteps = (kTiles + NW - 1) / NW;
-  static constexpr int kStepPix = 32 * NW;
-  // input rows step j reads: lo(j) .. hi(j)
-  __host__ __device__ static constexpr int lo(int j) { return ST * ((kStepPix * j) / OW); }
-  __host__ __device__ static constexpr int hi(int j) {
-    const int end = kStepPix * (j + 1) < kPix ? kStepPix * (j + 1) : kPix;
-    const int r = ST * ((end - 1) / OW) + 3;
-    return r < IH - 1 ? r : IH - 1;
-  }
-  // first row the step after j loads (its earlier rows are already in the ring)
-  __host__ __device__ static constexpr int first_new(int j) {
-    return (j + 1 == kSteps) ? 0 : (hi(j) + 1 > lo(j + 1) ? hi(j) + 1 : lo(j + 1));
-  }
-  __host__ __device__ static constexpr int last_new(int j) {
-    return (j + 1 == kSteps) ? hi(0) : hi(j + 1);
-  }
-  // ring rows: step j's rows and its successor's held at once
-  static constexpr int ring() {
-    int m = 0;
-    for (int j = 0; j < kSteps; ++j) {
-      const int span = (j + 1 < kSteps) ? hi(j + 1) - lo(j) + 1 : (IH - lo(j)) + hi(0) + 1;
-      m = span > m ? span : m;
-    }
-    return m;
-  }
-  // most rows one step's prefetch brings in
-  static constexpr int max_new() {
-    int m = 0;
-    for (int j = 0; j < kSteps; ++j) {
-      const int r = last_new(j) - first_new(j) + 1;
-      m = r > m ? r : m;
-    }
-    return m;
-  }
-};
 
 // (lo, hi) fp16 pair -> (fp16(lo * s0 + h0), fp16(hi * s1 + h1)): an f32 fma of
 // the fp16 input rounded once, one v_fma_mix per element
@@ -560,22 +371,16 @@ __device__ __forceinline__ int ring_off(int px, int c) {
 
 // conv4 (NW 4): its weights in LDS (32 KB) rather than 128 registers a lane,
 // so two of its latency-bound workgroups share a CU (2 waves a SIMD, <= 256
-// registers each); DTCONV4_WLDS 0 / DTCONV4_OCC 1 is round 3's register form
-#ifndef DTCONV4_WLDS
-#define DTCONV4_WLDS 1
-#endif
-#ifndef DTCONV4_OCC
-#define DTCONV4_OCC (DTCONV4_WLDS ? 2 : 1)
-#endif
+// registers each)
 template <int IH, int IW, int OH, int OW, int ST, int NW, int kIn, int kOut>
-__global__ void __launch_bounds__(64 * NW, NW == 4 ? DTCONV4_OCC : 1)   // 1: one wave per SIMD, the full register file
+__global__ void __launch_bounds__(64 * NW, NW == 4 ? 2 : 1)   // 1: one wave per SIMD, the full register file
 conv32_kernel(int n, const __half* __restrict__ x, const half8* __restrict__ wfrag,
               const float* __restrict__ bias, const float* __restrict__ prev_part,
               const float* __restrict__ in_gamma, const float* __restrict__ in_beta, float in_eps,
               __half* __restrict__ y, float* __restrict__ part,
               const float* __restrict__ out_gamma, const float* __restrict__ out_beta,
               float out_eps, float slope, WeightSplit ws) {
-  using G = ConvGeom<IH, IW, OH, OW, ST, NW>;
+  using G = RowStream<IH, IW, OH, OW, ST, 4, NW>;
   constexpr int kRing = G::ring();
   constexpr int kRowU4 = IW * 4;                  // 16-B chunks per input row
   constexpr int kRowBytes = IW * 64;
@@ -592,14 +397,7 @@ conv32_kernel(int n, const __half* __restrict__ x, const half8* __restrict__ wfr
   unsigned char* rb = reinterpret_cast<unsigned char*>(ring);
 
   const SplitPart sp = split_part(ws, n);
-  if (sp.set2) {
-    wfrag = static_cast<const half8*>(ws.wfrag);
-    bias = ws.bias;
-    in_gamma = ws.in_gamma;
-    in_beta = ws.in_beta;
-    out_gamma = ws.out_gamma;
-    out_beta = ws.out_beta;
-  }
+  if (sp.set2) use_set2(ws, wfrag, bias, in_gamma, in_beta, out_gamma, out_beta);
   const int send = sp.send;
   const int total = sp.my * G::kSteps;
   if (total == 0) return;
@@ -679,7 +477,7 @@ conv32_kernel(int n, const __half* __restrict__ x, const half8* __restrict__ wfr
 
   // weights and bias for the whole launch (row = out channel = lane & 31): in
   // registers, or for conv4 in LDS (kWL), read per MFMA
-  constexpr bool kWL = NW == 4 && DTCONV4_WLDS;
+  constexpr bool kWL = NW == 4;
   __shared__ __attribute__((aligned(16))) half8 wl[kWL ? 32 * 64 : 1];
   half8 wa[kWL ? 1 : 32];
   if constexpr (kWL) {
@@ -699,6 +497,8 @@ conv32_kernel(int n, const __half* __restrict__ x, const half8* __restrict__ wfr
   // two steps ahead of the MFMAs.
   auto step = [&](int g, int k, int j, u32x4 (&nxt)[kPre], const u32x4 (&cur)[kPre]) __attribute__((always_inline)) {
     const int ns = sample(k);
+    // (step_idx's arithmetic, written out: through the shared function the
+    // eval-mode conv3 kernel compiled to a slower instruction stream)
     const bool last_j = j + 1 == G::kSteps;
     const int k1 = last_j ? k + 1 : k, j1 = last_j ? 0 : j + 1;   // step g+1
     const bool last_j1 = j1 + 1 == G::kSteps;
@@ -709,11 +509,9 @@ conv32_kernel(int n, const __half* __restrict__ x, const half8* __restrict__ wfr
     if (!(DTCONV_SKIP & 1)) issue(nxt, k2, G::first_new(j1), G::last_new(j1));
 
     // this wave's tile
-    const int t = NW * j + wave;
-    const int p = 32 * t + col;
-    const bool valid = p < G::kPix;
-    const int pc = valid ? p : 0;
-    const int oy = pc / OW, ox = pc - oy * OW;
+    const TileIdx ti = tile_idx<G>(j, wave, col);
+    const int p = ti.p, pc = ti.pc, oy = ti.oy, ox = ti.ox;
+    const bool valid = ti.valid;
     int row[4];
 #pragma unroll
     for (int ky = 0; ky < 4; ++ky) row[ky] = ((k * IH + ST * oy + ky) % kRing) * kRowBytes;
@@ -756,115 +554,18 @@ conv32_kernel(int n, const __half* __restrict__ x, const half8* __restrict__ wfr
     if (kOut <= 1) {
       if (kOut == 0) centre_px32(v, s_c, j == 0 && wave == 0 && col == 0, j == 0, h);
       if (!(DTCONV_SKIP & 4)) store_px32<G::kPix>(y + (size_t)ns * G::kPix * CO, pc, v, h, valid);
-      if (kOut == 0 && valid && !(DTCONV_SKIP & 8)) {   // Welford over this lane's pixels
-        w_cnt += 1.0f;
-        const float inv = 1.0f / w_cnt;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float d = v[r] - w_mean[r];
-          w_mean[r] += d * inv;
-          w_m2[r] += d * (v[r] - w_mean[r]);
-        }
-      }
-      if (kOut == 0 && last_j) {
-        // merge the 32 lanes of each half (same 16 channels), then the waves
-#pragma unroll
-        for (int o = 1; o < 32; o <<= 1) {
-          const float nb = __shfl_xor(w_cnt, o, 32);
-          const float tot = w_cnt + nb;
-          const float fa = tot > 0.0f ? nb / tot : 0.0f, fb = tot > 0.0f ? w_cnt * nb / tot : 0.0f;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const float mb = __shfl_xor(w_mean[r], o, 32), m2b = __shfl_xor(w_m2[r], o, 32);
-            const float d = mb - w_mean[r];
-            w_mean[r] += d * fa;
-            w_m2[r] += m2b + d * d * fb;
-          }
-          w_cnt = tot;
-        }
-        if (col == 0)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int c = (r & 3) + 8 * (r >> 2) + 4 * h;
-            red[wave][c][0] = w_cnt;
-            red[wave][c][1] = w_mean[r];
-            red[wave][c][2] = w_m2[r];
-          }
-        __syncthreads();
-        if (tid < CO) {
-          float cnt = 0.0f, mean = 0.0f, m2 = 0.0f;
-          for (int w = 0; w < NW; ++w) {
-            const float nb = red[w][tid][0];
-            if (nb <= 0.0f) continue;
-            const float tot = cnt + nb, d = red[w][tid][1] - mean;
-            mean += d * (nb / tot);
-            m2 += red[w][tid][2] + d * d * (cnt * nb / tot);
-            cnt = tot;
-          }
-          float* pp = part + ((size_t)ns * CO + tid) * 3;
-          pp[0] = mean;
-          pp[1] = m2;
-          pp[2] = s_c[tid];
-        }
-        w_cnt = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) w_mean[r] = w_m2[r] = 0.0f;
-      }
+      if (kOut == 0 && valid && !(DTCONV_SKIP & 8))   // Welford over this lane's pixels
+        welford_add<false>(v, w_cnt, w_mean, w_m2);
+      if (kOut == 0 && last_j)
+        stats_flush<NW>(w_cnt, w_mean, w_m2, red, s_c, part + (size_t)ns * CO * 3, tid, wave, col,
+                        h);
     } else {   // the whole sample is in this step: BatchNorm of a batch of one, flatten
-      if (kOut == 2) {
-        // per wave, two passes over its own 32 pixels (shuffles only: exact
-        // mean, then M2 about it); the waves' (n, mean, M2) merged with
-        // Chan's formula by threads < CO: two barriers a sample, not four
-        // level by level over the 16 channels: each level's 16 shuffles are
-        // in flight together (channel by channel, every shuffle waited for the
-        // one before it: 160 dependent LDS round trips, 16k cycles a sample);
-        // each channel's sums keep their order, so the bits are unchanged
-        float nw = valid ? 1.0f : 0.0f;
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) nw += __shfl_xor(nw, o, 32);
-        const float inw = nw > 0.0f ? 1.0f / nw : 0.0f;
-        float sum[16], m2[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sum[r] = valid ? v[r] : 0.0f;
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) sum[r] += __shfl_xor(sum[r], o, 32);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float d = valid ? v[r] - sum[r] * inw : 0.0f;
-          m2[r] = d * d;
-        }
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) m2[r] += __shfl_xor(m2[r], o, 32);
-        if (col == 0) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int c = (r & 3) + 8 * (r >> 2) + 4 * h;
-            red[wave][c][0] = nw;
-            red[wave][c][1] = sum[r] * inw;
-            red[wave][c][2] = m2[r];
-          }
-        }
-        __syncthreads();
-        if (tid < CO) {
-          float cnt = 0.0f, mean = 0.0f, m2 = 0.0f;
-          for (int w = 0; w < NW; ++w) {
-            const float nb = red[w][tid][0];
-            if (nb <= 0.0f) continue;
-            const float tot = cnt + nb, d = red[w][tid][1] - mean;
-            mean += d * (nb / tot);
-            m2 += red[w][tid][2] + d * d * (cnt * nb / tot);
-            cnt = tot;
-          }
-          const float sc = out_gamma[tid] / sqrtf(m2 / (float)G::kPix + out_eps);
+      if (kOut == 2)   // exact statistics of the sample -> the norm's scale and shift
+        twopass_stats<NW>(v, valid, red, tid, wave, col, h, [&](const Moments& m) {
+          const float sc = out_gamma[tid] / sqrtf(m.m2 / (float)G::kPix + out_eps);
           s_rstd[tid] = sc;
-          s_mean[tid] = out_beta[tid] - mean * sc;   // the shift
-        }
-        __syncthreads();
-      }
+          s_mean[tid] = out_beta[tid] - m.mean * sc;   // the shift
+        });
       {   // branch-free (see store_px32): invalid lanes store past the sample
         constexpr int kBytes = G::kPix * CO * 2;
         const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -904,15 +605,7 @@ conv32_kernel(int n, const __half* __restrict__ x, const half8* __restrict__ wfr
     issue(pb, G::kSteps == 1 ? 1 : 0, G::first_new(0), G::last_new(0));
   __syncthreads();
 
-  int k = 0, j = 0;
-  for (int g = 0; g < total; g += 2) {
-    step(g, k, j, pa, pb);
-    if (++j == G::kSteps) { j = 0; ++k; }
-    if (g + 1 < total) {
-      step(g + 1, k, j, pb, pa);
-      if (++j == G::kSteps) { j = 0; ++k; }
-    }
-  }
+  run_steps<G::kSteps>(total, pa, pb, step);
 }
 
 template <int IH, int IW, int OH, int OW, int ST, int NW, int kIn, int kOut>
@@ -922,15 +615,7 @@ int launch_conv32(int n, const void* x, const void* wfrag, const float* bias,
                   float slope, hipStream_t s, WeightSplit ws, int n0) {
   auto kern = conv32_kernel<IH, IW, OH, OW, ST, NW, kIn, kOut>;
   static int grid = 0;   // resident workgroups: one wave of them, persistent
-  if (!grid) {
-    int dev = 0, cus = 256, per = 1;
-    if (hipGetDevice(&dev) == hipSuccess)
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, 64 * NW, 0) != hipSuccess ||
-        per < 1)
-      per = 1;
-    grid = per * cus;
-  }
+  if (!grid) grid = resident_grid(kern, 64 * NW, 0);
   const int g = split_grid(ws, n, n0, grid);
   hipLaunchKernelGGL(kern, dim3(g), dim3(64 * NW), 0, s, n, (const __half*)x, (const half8*)wfrag,
                      bias, prev_part, ig, ibt, ieps, (__half*)y, part, og, obt, oeps,
@@ -941,6 +626,13 @@ int launch_conv32(int n, const void* x, const void* wfrag, const float* bias,
 // waves (tiles per step) per layer: conv2 / conv3 two (2-3 rings per CU), conv4
 // four (its 4 tiles in one step for the in-kernel norm)
 constexpr int kConv2Waves = 2, kConv3Waves = 2, kConv4Waves = 4;
+// the streams' geometry, pinned: steps a sample, ring rows, most rows a prefetch
+using Conv2Stream = RowStream<57, 77, 27, 37, 2, 4, kConv2Waves>;
+using Conv3Stream = RowStream<27, 37, 12, 17, 2, 4, kConv3Waves>;
+using Conv4Stream = RowStream<12, 17, 9, 14, 1, 4, kConv4Waves>;
+static_assert(Conv2Stream::kSteps == 16 && Conv2Stream::ring() == 13 && Conv2Stream::max_new() == 6);
+static_assert(Conv3Stream::kSteps == 4 && Conv3Stream::ring() == 20 && Conv3Stream::max_new() == 10);
+static_assert(Conv4Stream::kSteps == 1 && Conv4Stream::ring() == 24 && Conv4Stream::max_new() == 12);
 
 }  // namespace
 
@@ -949,10 +641,7 @@ template <bool kIdx>
 int conv1_launch(const void* ring, int32_t n, int32_t slots, const int32_t* order,
                  const void* wfrag, const float* bias, const dt_conv_set* set2, void* y,
                  float* partials, float slope, void* stream) {
-  if (!ring || !wfrag || !bias || !y || !order || n < 0 || slots < 3) return DT_E_ARG;
-  for (int i = 0; i < 3; ++i)
-    if (order[i] < 0 || order[i] >= slots) return DT_E_ARG;
-  if (set2 && (set2->n0 < 0 || set2->n0 > n || !set2->wfrag || !set2->bias)) return DT_E_ARG;
+  if (!conv1_args_ok(ring, n, slots, order, wfrag, bias, set2, y)) return DT_E_ARG;
   if (n == 0) return DT_OK;
   static int grid = 0;   // resident workgroups, persistent
   if (!grid) grid = resident_grid(conv1s_kernel<true, kIdx>, kSThreads, DTCONV1_PER);
@@ -1031,10 +720,10 @@ extern "C" int dt_conv32_split(int32_t layer, int32_t n, const void* x, const vo
   if (!x || !wfrag || !bias || !y || n < 0) return DT_E_ARG;
   const bool in = prev_part != nullptr;
   if (in && (!in_gamma || !in_beta)) return DT_E_ARG;
-  if (set2 && (set2->n0 < 0 || set2->n0 > n || !set2->wfrag || !set2->bias ||
-               (in && (!set2->in_gamma || !set2->in_beta)) ||
-               ((out_gamma != nullptr) != (set2->out_gamma != nullptr)) ||
-               ((out_beta != nullptr) != (set2->out_beta != nullptr))))
+  // the second set carries the output norm exactly where the first does
+  if (!set2_ok(set2, n, in, false) ||
+      (set2 && (((out_gamma != nullptr) != (set2->out_gamma != nullptr)) ||
+                ((out_beta != nullptr) != (set2->out_beta != nullptr)))))
     return DT_E_ARG;
   if (n == 0) return DT_OK;
   const WeightSplit ws = weight_split(set2);

@@ -107,7 +107,7 @@ struct Hlb {
 
 // One output pixel's 32 channels into an HLB image (OW_ wide, its consumer's
 // stride SN) from a 32x32 MFMA tile (lane = pixel column, register r =
-// channel (r&3) + 8*(r>>2) + 4h): v_permlane32_swap pairs the two half-waves'
+// channel (r&3) + 8*(r>>2) + 4h): swap_halves pairs the two half-waves'
 // 4-channel groups, so a lane holds channels 16m + 8h .. +7 = block 2m + h
 // and stores it as one 16-B chunk of hi and one of lo.  Branch-free: an
 // invalid lane's offset lies past the sample and the buffer store is dropped.
@@ -121,17 +121,7 @@ __device__ __forceinline__ void store_hlb(unsigned char* sample, int oy, int ox,
   for (int q = 0; q < 4; ++q)
 #pragma unroll
     for (int e = 0; e < 2; ++e) split2(v[4 * q + 2 * e], v[4 * q + 2 * e + 1], uh[q][e], ul[q][e]);
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      auto r = __builtin_amdgcn_permlane32_swap(uh[2 * m][e], uh[2 * m + 1][e], false, false);
-      uh[2 * m][e] = r[0];
-      uh[2 * m + 1][e] = r[1];
-      r = __builtin_amdgcn_permlane32_swap(ul[2 * m][e], ul[2 * m + 1][e], false, false);
-      ul[2 * m][e] = r[0];
-      ul[2 * m + 1][e] = r[1];
-    }
+  swap_halves(uh, ul);
   const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(sample, 0, kBytes, 0x00020000);
   const int base = valid ? L::off(oy, h, 0, ox) : kBytes;
 #pragma unroll
@@ -143,61 +133,8 @@ __device__ __forceinline__ void store_hlb(unsigned char* sample, int oy, int ox,
   }
 }
 
-// Per-lane Welford statistics of a 32x32 tile's 16 channels merged over the
-// sample: the lanes of each half (shuffles), then the waves (red, one
-// barrier), written as (mean, M2, c) per channel by threads < CO.
-template <int NW>
-__device__ __forceinline__ void stats_flush(float& w_cnt, float (&w_mean)[16], float (&w_m2)[16],
-                                            float (*red)[CO][3], const float* s_c, float* out,
-                                            int tid, int wave, int col, int h) {
-#pragma unroll
-  for (int o = 1; o < 32; o <<= 1) {
-    const float nb = __shfl_xor(w_cnt, o, 32);
-    const float tot = w_cnt + nb;
-    const float fa = tot > 0.0f ? nb / tot : 0.0f, fb = tot > 0.0f ? w_cnt * nb / tot : 0.0f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float mb = __shfl_xor(w_mean[r], o, 32), m2b = __shfl_xor(w_m2[r], o, 32);
-      const float d = mb - w_mean[r];
-      w_mean[r] += d * fa;
-      w_m2[r] += m2b + d * d * fb;
-    }
-    w_cnt = tot;
-  }
-  if (col == 0)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int c = (r & 3) + 8 * (r >> 2) + 4 * h;
-      red[wave][c][0] = w_cnt;
-      red[wave][c][1] = w_mean[r];
-      red[wave][c][2] = w_m2[r];
-    }
-  __syncthreads();
-  if (tid < CO) {
-    float cnt = 0.0f, mean = 0.0f, m2 = 0.0f;
-    for (int w = 0; w < NW; ++w) {
-      const float nb = red[w][tid][0];
-      if (nb <= 0.0f) continue;
-      const float tot = cnt + nb, d = red[w][tid][1] - mean;
-      mean += d * (nb / tot);
-      m2 += red[w][tid][2] + d * d * (cnt * nb / tot);
-      cnt = tot;
-    }
-    float* pp = out + tid * 3;
-    pp[0] = mean;
-    pp[1] = m2;
-    pp[2] = s_c[tid];
-  }
-  w_cnt = 0.0f;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) w_mean[r] = w_m2[r] = 0.0f;
-}
-
 // ---- conv1 -------------------------------------------------------------------------
-constexpr int kXPxB = 6;                  // bytes a ring pixel: 3 fp16 channels (hi or lo)
-constexpr int kXRowB = IW * kXPxB;        // 960 B a ring row
-constexpr int kXMfma = 12, kXGrp = 3;     // k steps a tile (K 192), a B-fragment group
-
+// The row stream of dtconv_common.h (c1) with a hi ring and a lo ring.
 // kIdx: palette-index frames (u8), decoded through an 8-entry (hi, lo) table
 template <bool kIdx>
 __global__ void __launch_bounds__(kSThreads, 2)   // 2 waves / SIMD: <= 256 registers
@@ -205,11 +142,10 @@ conv1x_kernel(int n, const void* __restrict__ ring, int slots, int s0, int s1, i
               const half8* __restrict__ wfrag, const float* __restrict__ bias,
               unsigned char* __restrict__ y, float* __restrict__ partials, float slope,
               WeightSplit ws) {
-  using Elem = typename std::conditional<kIdx, uint8_t, float>::type;
-  using Item = typename std::conditional<kIdx, uint32_t, float4>::type;
-  const Elem* __restrict__ ringT = static_cast<const Elem*>(ring);
-  __shared__ __attribute__((aligned(16))) unsigned char rbh[kSRing * kXRowB];
-  __shared__ __attribute__((aligned(16))) unsigned char rbl[kSRing * kXRowB];
+  using Item = c1::Item<kIdx>;
+  const Elem<kIdx>* __restrict__ ringT = static_cast<const Elem<kIdx>*>(ring);
+  __shared__ __attribute__((aligned(16))) unsigned char rbh[kSRing * kSRowB];
+  __shared__ __attribute__((aligned(16))) unsigned char rbl[kSRing * kSRowB];
   __shared__ uint32_t s_hl[8];
   __shared__ float red[kSW][CO][3];
   __shared__ float s_bias[CO];
@@ -225,32 +161,9 @@ conv1x_kernel(int n, const void* __restrict__ ring, int slots, int s0, int s1, i
   const int total = sp.my * kSSteps;
   if (total == 0) return;
   auto sample = [&](int k) __attribute__((always_inline)) { return sp.sbeg + sp.bid + k * sp.gdim; };
-  const size_t plane = (size_t)IH * IW;
-
-  int it_r[kSPre], it_off[kSPre], it_lds[kSPre];
-#pragma unroll
-  for (int i = 0; i < kSPre; ++i) {
-    const int q = tid + i * kSThreads;
-    it_r[i] = q / kSQuads;
-    it_off[i] = it_r[i] * IW + 4 * (q - it_r[i] * kSQuads);
-    it_lds[i] = 4 * kXPxB * (q - it_r[i] * kSQuads);
-  }
-  // rows r0..r1 of the k-th sample into registers (conv1s_kernel's issue:
-  // every load on every path, sample clamped, row-free steps read row 0)
+  const Items its = items(tid);
   auto issue = [&](Item (&pre)[kSPre][3], int k, int r0, int r1) __attribute__((always_inline)) {
-    const int rows = r1 - r0 + 1;
-    const int ns = sample(k) < send ? sample(k) : send - 1;
-    const Elem* base = ringT + (size_t)ns * slots * plane + (size_t)(rows > 0 ? r0 : 0) * IW;
-    const Elem* p0 = base + (size_t)s0 * plane;
-    const Elem* p1 = base + (size_t)s1 * plane;
-    const Elem* p2 = base + (size_t)s2 * plane;
-#pragma unroll
-    for (int i = 0; i < kSPre; ++i) {
-      const int off = it_r[i] < rows ? it_off[i] : 0;
-      pre[i][0] = *reinterpret_cast<const Item*>(p0 + off);
-      pre[i][1] = *reinterpret_cast<const Item*>(p1 + off);
-      pre[i][2] = *reinterpret_cast<const Item*>(p2 + off);
-    }
+    c1::issue<kIdx>(pre, its, ringT, slots, s0, s1, s2, sample(k), send, r0, r1);
   };
   // a load item's 4 pixels of one frame as (hi, lo) words
   auto px4 = [&](const Item& it, uint32_t (&o)[4]) __attribute__((always_inline)) {
@@ -270,16 +183,16 @@ conv1x_kernel(int n, const void* __restrict__ ring, int slots, int s0, int s1, i
     const int rows = r1 - r0 + 1;
 #pragma unroll
     for (int i = 0; i < kSPre; ++i) {
-      if (it_r[i] >= rows) continue;
-      const int slot = (k * IH + r0 + it_r[i]) & (kSRing - 1);
+      if (its.r[i] >= rows) continue;
+      const int slot = (k * IH + r0 + its.r[i]) & (kSRing - 1);
       uint32_t av[4], bv[4], cv[4];
       px4(pre[i][0], av);
       px4(pre[i][1], bv);
       px4(pre[i][2], cv);
       const uint32_t f[12] = {av[0], bv[0], cv[0], av[1], bv[1], cv[1],
                               av[2], bv[2], cv[2], av[3], bv[3], cv[3]};
-      uint2* dh = reinterpret_cast<uint2*>(rbh + slot * kXRowB + it_lds[i]);   // 8-B aligned
-      uint2* dl = reinterpret_cast<uint2*>(rbl + slot * kXRowB + it_lds[i]);
+      uint2* dh = reinterpret_cast<uint2*>(rbh + slot * kSRowB + its.lds[i]);   // 8-B aligned
+      uint2* dl = reinterpret_cast<uint2*>(rbl + slot * kSRowB + its.lds[i]);
 #pragma unroll
       for (int e = 0; e < 3; ++e) {
         dh[e] = make_uint2(hi_pair(f[4 * e], f[4 * e + 1]), hi_pair(f[4 * e + 2], f[4 * e + 3]));
@@ -288,24 +201,10 @@ conv1x_kernel(int n, const void* __restrict__ ring, int slots, int s0, int s1, i
     }
   };
 
-  // A fragments, hi and lo halves (K 192 as conv1s_kernel: step s covers
-  // kernel row 2(s/3) + h and 8 of its 24 (kx, c) values, t = 8(s%3) + j),
-  // gathered once from dt_conv1's fragment layout
-  half8 wah[kXMfma], wal[kXMfma];
-  {
-    const _Float16* wh = reinterpret_cast<const _Float16*>(wfrag);
-    const _Float16* wl = wh + 16 * 64 * 8;
-    const int co = lane & 31, hh = lane >> 5;
-#pragma unroll
-    for (int s = 0; s < kXMfma; ++s)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int ky = 2 * (s / 3) + hh, t = 8 * (s % 3) + e, kx = t / 3, c = t % 3;
-        const int s1 = 2 * ky + kx / 4, l1 = co + 32 * ((kx & 3) >> 1), j1 = 4 * (kx & 1) + c;
-        wah[s][e] = wh[(s1 * 64 + l1) * 8 + j1];
-        wal[s][e] = wl[(s1 * 64 + l1) * 8 + j1];
-      }
-  }
+  // A fragments, hi and lo halves of dt_conv1's fragment layout
+  half8 wah[kSMfma], wal[kSMfma];
+  gather_a(wah, reinterpret_cast<const _Float16*>(wfrag));
+  gather_a(wal, reinterpret_cast<const _Float16*>(wfrag) + 16 * 64 * 8);
   if (tid < CO) s_bias[tid] = bias[tid];
   if (kIdx && tid < 8) s_hl[tid] = hl16(dr::kPalGray[tid]);
   float w_cnt = 0.0f, w_mean[16], w_m2[16];
@@ -314,16 +213,12 @@ conv1x_kernel(int n, const void* __restrict__ ring, int slots, int s0, int s1, i
 
   auto step = [&](int g, int k, int j, Item (&nxt)[kSPre][3], const Item (&cur)[kSPre][3]) __attribute__((always_inline)) {
     const int ns = sample(k);
-    const bool last_j = j + 1 == kSSteps;
-    const int k1 = last_j ? k + 1 : k, j1 = last_j ? 0 : j + 1;   // step g+1
-    const int k2 = (j1 + 1 == kSSteps) ? k1 + 1 : k1;             // step g+2
-    issue(nxt, k2, s_first_new(j1), s_last_new(j1));
+    const StepIdx si = step_idx<Stream>(k, j);
+    issue(nxt, si.k2, Stream::first_new(si.j1), Stream::last_new(si.j1));
 
-    const int t = kSW * j + wave;
-    const int p = 32 * t + col;
-    const bool valid = p < kSPix;
-    const int pc = valid ? p : 0;
-    const int oy = pc / OW, ox = pc - oy * OW;
+    const TileIdx ti = tile_idx<Stream>(j, wave, col);
+    const int oy = ti.oy, ox = ti.ox;
+    const bool valid = ti.valid;
     const int rbase = k * IH + 2 * oy;
     const int cx = 12 * ox;
     f32x16 acc0, acc1;
@@ -332,12 +227,12 @@ conv1x_kernel(int n, const void* __restrict__ ring, int slots, int s0, int s1, i
       acc0[r] = s_bias[(r & 3) + 8 * (r >> 2) + 4 * h];
       acc1[r] = 0.0f;
     }
-    half8 bqh[2][kXGrp], bql[2][kXGrp];
-    auto ld = [&](half8 (&bh)[kXGrp], half8 (&bl)[kXGrp], int gy) __attribute__((always_inline)) {
+    half8 bqh[2][kSGrp], bql[2][kSGrp];
+    auto ld = [&](half8 (&bh)[kSGrp], half8 (&bl)[kSGrp], int gy) __attribute__((always_inline)) {
       using u32x4a = __attribute__((ext_vector_type(4), aligned(4))) uint32_t;
 #pragma unroll
-      for (int i = 0; i < kXGrp; ++i) {   // row 2gy + h, bytes 12 ox + 16 i: 4-B aligned
-        const int off = ((rbase + 2 * gy + h) & (kSRing - 1)) * kXRowB + cx + 16 * i;
+      for (int i = 0; i < kSGrp; ++i) {   // row 2gy + h, bytes 12 ox + 16 i: 4-B aligned
+        const int off = ((rbase + 2 * gy + h) & (kSRing - 1)) * kSRowB + cx + 16 * i;
         bh[i] = __builtin_bit_cast(half8, *reinterpret_cast<const u32x4a*>(rbh + off));
         bl[i] = __builtin_bit_cast(half8, *reinterpret_cast<const u32x4a*>(rbl + off));
       }
@@ -348,8 +243,8 @@ conv1x_kernel(int n, const void* __restrict__ ring, int slots, int s0, int s1, i
       if (gy < 3) ld(bqh[(gy + 1) & 1], bql[(gy + 1) & 1], gy + 1);
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int i = 0; i < kXGrp; ++i) {
-        const int s = kXGrp * gy + i;
+      for (int i = 0; i < kSGrp; ++i) {
+        const int s = kSGrp * gy + i;
         acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wah[s], bqh[gy & 1][i], acc0, 0, 0, 0);
         acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wah[s], bql[gy & 1][i], acc1, 0, 0, 0);
         acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wal[s], bqh[gy & 1][i], acc1, 0, 0, 0);
@@ -361,41 +256,24 @@ conv1x_kernel(int n, const void* __restrict__ ring, int slots, int s0, int s1, i
     for (int r = 0; r < 16; ++r) v[r] = lrelu2(acc0[r] + acc1[r] * kLoInv, slope);
     centre_px32(v, s_c, j == 0 && wave == 0 && col == 0, j == 0, h);
     store_hlb<OH, OW, 2>(y + (size_t)ns * OH * Hlb<OW, 2>::kRow, oy, ox, v, h, valid);
-    if (valid) {   // Welford over this lane's pixels
-      w_cnt += 1.0f;
-      const float inv = 1.0f / w_cnt;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float d = v[r] - w_mean[r];
-        w_mean[r] += d * inv;
-        w_m2[r] += d * (v[r] - w_mean[r]);
-      }
-    }
-    if (last_j)
+    if (valid) welford_add<false>(v, w_cnt, w_mean, w_m2);   // over this lane's pixels
+    if (si.last_j)
       stats_flush<kSW>(w_cnt, w_mean, w_m2, red, s_c, partials + (size_t)ns * CO * 3, tid, wave,
                        col, h);
     // step g+1's rows into the rings (slots no wave reads in this step); the
     // barrier publishes them
-    if (g + 1 < total) commit(cur, k1, s_first_new(j), s_last_new(j));
+    if (g + 1 < total) commit(cur, si.k1, Stream::first_new(j), Stream::last_new(j));
     __syncthreads();
   };
 
   Item pa[kSPre][3], pb[kSPre][3];
-  issue(pa, 0, 0, s_hi(0));
+  issue(pa, 0, 0, Stream::hi(0));
   if (kIdx) __syncthreads();   // s_hl
-  commit(pa, 0, 0, s_hi(0));
-  if (total > 1) issue(pb, kSSteps == 1 ? 1 : 0, s_first_new(0), s_last_new(0));
+  commit(pa, 0, 0, Stream::hi(0));
+  if (total > 1) issue(pb, kSSteps == 1 ? 1 : 0, Stream::first_new(0), Stream::last_new(0));
   __syncthreads();
   __builtin_amdgcn_s_waitcnt(0);   // see conv1s_kernel: keeps the loop's vmcnt waits exact
-  int k = 0, j = 0;
-  for (int g = 0; g < total; g += 2) {
-    step(g, k, j, pa, pb);
-    if (++j == kSSteps) { j = 0; ++k; }
-    if (g + 1 < total) {
-      step(g + 1, k, j, pb, pa);
-      if (++j == kSSteps) { j = 0; ++k; }
-    }
-  }
+  run_steps<kSSteps>(total, pa, pb, step);
 }
 
 // ---- conv2..conv4 --------------------------------------------------------------------
@@ -431,14 +309,7 @@ conv32x_kernel(int n, const unsigned char* __restrict__ x, const float* __restri
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int col = lane & 31, h = lane >> 5;
   const SplitPart sp = split_part(ws, n);
-  if (sp.set2) {
-    wsrc = static_cast<const float*>(ws.wfrag);
-    bias = ws.bias;
-    in_gamma = ws.in_gamma;
-    in_beta = ws.in_beta;
-    out_gamma = ws.out_gamma;
-    out_beta = ws.out_beta;
-  }
+  if (sp.set2) use_set2(ws, wsrc, bias, in_gamma, in_beta, out_gamma, out_beta);
   if (sp.my == 0) return;
   const int send = sp.send;
   auto sample = [&](int k) __attribute__((always_inline)) {
@@ -538,66 +409,16 @@ conv32x_kernel(int n, const unsigned char* __restrict__ x, const float* __restri
       const int pc = valid ? p : 0, oy = pc / OW_;
       store_hlb<OH_, OW_, SN>(static_cast<unsigned char*>(y) + (size_t)ns * OH_ * Hlb<OW_, SN>::kRow,
                               oy, pc - oy * OW_, v, h, valid);
-      if (valid) {
-        w_cnt += 1.0f;
-        const float inv = 1.0f / w_cnt;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const float d = v[q] - w_mean[q];
-          w_mean[q] += d * inv;
-          w_m2[q] += d * (v[q] - w_mean[q]);
-        }
-      }
+      if (valid) welford_add<false>(v, w_cnt, w_mean, w_m2);
       if (r + 1 == kRounds)
         stats_flush<NW>(w_cnt, w_mean, w_m2, red, s_c, part + (size_t)ns * CO * 3, tid, wave, col,
-                       h);
+                        h);
     } else {
-      // exact two-pass statistics: per wave over its 32 pixels (shuffles),
-      // the waves merged with Chan's formula by threads < CO
-      float nw = valid ? 1.0f : 0.0f;
-#pragma unroll
-      for (int o = 16; o > 0; o >>= 1) nw += __shfl_xor(nw, o, 32);
-      const float inw = nw > 0.0f ? 1.0f / nw : 0.0f;
-      float sum[16], m2[16];
-#pragma unroll
-      for (int q = 0; q < 16; ++q) sum[q] = valid ? v[q] : 0.0f;
-#pragma unroll
-      for (int o = 16; o > 0; o >>= 1)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) sum[q] += __shfl_xor(sum[q], o, 32);
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const float d = valid ? v[q] - sum[q] * inw : 0.0f;
-        m2[q] = d * d;
-      }
-#pragma unroll
-      for (int o = 16; o > 0; o >>= 1)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) m2[q] += __shfl_xor(m2[q], o, 32);
-      if (col == 0)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const int c = (q & 3) + 8 * (q >> 2) + 4 * h;
-          red[wave][c][0] = nw;
-          red[wave][c][1] = sum[q] * inw;
-          red[wave][c][2] = m2[q];
-        }
-      __syncthreads();
-      if (tid < CO) {
-        float cnt = 0.0f, mean = 0.0f, mm = 0.0f;
-        for (int w = 0; w < NW; ++w) {
-          const float nb = red[w][tid][0];
-          if (nb <= 0.0f) continue;
-          const float tot = cnt + nb, d = red[w][tid][1] - mean;
-          mean += d * (nb / tot);
-          mm += red[w][tid][2] + d * d * (cnt * nb / tot);
-          cnt = tot;
-        }
-        s_omean[tid] = mean;
-        s_osc[tid] = out_gamma[tid] / sqrtf(mm / (float)kPix + out_eps);
+      twopass_stats<NW>(v, valid, red, tid, wave, col, h, [&](const Moments& m) {
+        s_omean[tid] = m.mean;
+        s_osc[tid] = out_gamma[tid] / sqrtf(m.m2 / (float)kPix + out_eps);
         s_obeta[tid] = out_beta[tid];
-      }
-      __syncthreads();
+      });
       constexpr int kBytes = kPix * CO * 4;
       const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(
           static_cast<float*>(y) + (size_t)ns * CO * kPix, 0, kBytes, 0x00020000);
@@ -996,10 +817,7 @@ template <bool kIdx>
 int conv1x_launch(const void* ring, int32_t n, int32_t slots, const int32_t* order,
                   const void* wfrag, const float* bias, const dt_conv_set* set2, void* y,
                   float* partials, float slope, void* stream) {
-  if (!ring || !wfrag || !bias || !y || !partials || !order || n < 0 || slots < 3) return DT_E_ARG;
-  for (int i = 0; i < 3; ++i)
-    if (order[i] < 0 || order[i] >= slots) return DT_E_ARG;
-  if (set2 && (set2->n0 < 0 || set2->n0 > n || !set2->wfrag || !set2->bias)) return DT_E_ARG;
+  if (!partials || !conv1_args_ok(ring, n, slots, order, wfrag, bias, set2, y)) return DT_E_ARG;
   if (n == 0) return DT_OK;
   static int grid = 0;
   if (!grid) grid = resident_grid(conv1x_kernel<kIdx>, kSThreads, 0);
@@ -1090,9 +908,7 @@ extern "C" int dt_conv32x_split(int32_t layer, int32_t n, const void* x, const f
   if (!x || !wfrag || !bias || !y || !prev_part || !in_gamma || !in_beta || n < 0) return DT_E_ARG;
   const bool last = layer == 4;
   if (last ? (!out_gamma || !out_beta) : !part) return DT_E_ARG;
-  if (set2 && (set2->n0 < 0 || set2->n0 > n || !set2->wfrag || !set2->bias || !set2->in_gamma ||
-               !set2->in_beta || (last && (!set2->out_gamma || !set2->out_beta))))
-    return DT_E_ARG;
+  if (!set2_ok(set2, n, true, last)) return DT_E_ARG;
   if (n == 0) return DT_OK;
   const WeightSplit ws = weight_split(set2);
   const int n0 = set2 ? set2->n0 : n;
