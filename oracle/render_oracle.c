@@ -13,8 +13,9 @@
  *     stack-based hysteresis as OpenCV implements it.
  * cv2 is absent (and unpinned by any reference fixture): HSV is pinned against
  * colorsys to +-1, dilation against scipy.ndimage, bresenham against the
- * reference's golden vectors; Canny is pinned only by this restatement
- * ("parity unpinned" for the edge map).
+ * reference's golden vectors; Canny against an independent numpy / scipy
+ * restatement of the algorithm (tests/canny_ref.py), on inputs that tell it
+ * from its near-misses.  Parity with an OpenCV binary stays unchecked.
  * Compiled with -ffp-contract=off -fno-builtin (see Makefile).
  */
 #include <math.h>

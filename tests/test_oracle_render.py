@@ -3,8 +3,9 @@
 cv2 is absent, so each OpenCV piece is pinned against an independent source:
 bresenham against the reference's own generator (golden vectors), HSV against
 colorsys (+-1 from OpenCV's fixed point), dilation against scipy.ndimage; the
-Canny edge map has no independent implementation here (parity unpinned), so
-only its invariants are checked."""
+Canny edge map against an independent numpy / scipy restatement of the
+algorithm (tests/canny_ref.py, in tests/test_canny_ref.py; its invariants
+here).  Parity with an OpenCV binary itself stays unchecked."""
 import colorsys
 import math
 
